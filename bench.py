@@ -21,13 +21,22 @@ reported as per_gpu).  At N > 1 a second leg (c4_shards) runs BASELINE config 4:
 a 1 GiB mixed-frame shard per GPU, aggregate and per-GPU GiB/s.
 
 Prints ONE JSON line on rank 0.  Roofline: 2 x payload bytes per launch (read +
-write) / mean kernel duration (HIP events on the launch stream) vs 8.0 TB/s, next
-to in-bench frame-free stream ceilings (hand-written kernels, same rotation) and the
-same kernel out of place and with src misaligned against dst (roofline.shapes).
-After the timed region: the timed entry is checked (involution + every frame's
-keystream), BASELINE config 5's host-to-host rate is measured (rank 0, N = 1), and
-cpu_baseline times the oracle's restatement of the reference loop on this host,
-rank 0, N = 1 only, bounded sample (see --cpu-seconds).
+write) / mean kernel duration (HIP events on the launch stream) vs 8.0 TB/s.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed
+steps, --dump-outputs DIR when given (a seeded sample of what the last timed step left
+in its dst buffer, DIR/<name>.npy, float32; same arguments, same inputs, so two builds
+compare output for output), and the line.  Everything else runs only with --full, after
+the timed region, and fills the fields that are null in a plain line: two batches in
+flight on two streams (pipelined_2stream), in-bench frame-free stream ceilings
+(hand-written kernels, same rotation) and the same kernel out of place and with src
+misaligned against dst (roofline.ceilings / roofline.shapes), the check of the timed
+entry (involution + every frame's keystream: verified), the BASELINE config 4 leg at
+N > 1, BASELINE config 5's host-to-host rate (rank 0, N = 1), and cpu_baseline, the
+oracle's restatement of the reference loop timed on this host, rank 0, N = 1 only,
+bounded sample (see --cpu-seconds).  The options that switch single legs off or size
+them (--no-copy-ceiling, --c5-gib, --cpu-seconds, --no-pipelined-probe, --no-shard-leg)
+act within --full.
 """
 
 from __future__ import annotations
@@ -62,6 +71,13 @@ def parse_args():
     p.add_argument("--warmup", type=int, default=20)
     p.add_argument("--workload", choices=sorted(WORKLOADS), default="c2")
     p.add_argument("--rotation-bytes", type=int, default=2 << 30, help="distinct device bytes the steps rotate over")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every secondary leg: the check of the timed entry, the "
+                        "two-stream figure, the stream ceilings and shape points, the config 4 / config 5 legs and "
+                        "the CPU baseline (a plain run only times the headline)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed (its dst buffer; a fixed "
+                        "seeded sample when it is large) to DIR/<name>.npy as float32")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (0 disables)")
     p.add_argument("--unroll", type=int, default=None)
     p.add_argument("--max-blocks", type=int, default=None)
@@ -211,6 +227,26 @@ def shape_points(torch, entry, local, batches, total, nframes, stream, steps):
         torch.cuda.synchronize()
         out[name] = round(2.0 * n_bytes / (e0.elapsed_time(e1) / steps * 1e-3) / 1e9, 1)
     return out
+
+
+DUMP_SAMPLE = 4 << 20          # bytes of a larger output kept by --dump-outputs (16 MiB as float32)
+
+
+def dump_outputs(torch, out_dir: str, dst, rank: int, world: int) -> None:
+    """--dump-outputs: the bytes the last timed step left in its dst buffer -- what a caller of
+    netc_gpu_mask_batch receives -- as float32 in out_dir/masked_payload.npy (one file per rank
+    at N > 1).  A buffer above DUMP_SAMPLE / N bytes is sampled at fixed positions: both ends
+    whole, the rest at indices drawn from a seeded generator, in ascending order."""
+    n = dst.numel()
+    keep = DUMP_SAMPLE // world
+    if n > keep:
+        edge = keep // 8
+        mid = np.sort(np.random.default_rng(6455).integers(edge, n - edge, size=keep - 2 * edge))
+        idx = np.concatenate([np.arange(edge), mid, np.arange(n - edge, n)])
+        dst = dst[torch.from_numpy(idx).to(dst.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    name = "masked_payload.npy" if world == 1 else f"masked_payload_rank{rank}.npy"
+    np.save(os.path.join(out_dir, name), dst.cpu().numpy().astype(np.float32))
 
 
 def verify_step(torch, nm, batch, total, nframes, off_h, keys_h, stream):
@@ -571,10 +607,15 @@ def main():
     # Timed region: K back-to-back launches on one stream (timed_steps).
     elapsed, kern_own = timed_steps(torch, step, args.steps, args.warmup, stream, device, world)
 
-    # secondary figure: the same steps with two batches in flight on two HIP streams
-    # (independent batches, as a serving loop would pipeline them); not the headline
+    nlast = (args.warmup + args.steps - 1) % nb   # the batch the last timed step masked
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, batches[nlast][0], rank, world)
+
+    # From here to the result line every leg is secondary and runs only with --full.
+    # First the same steps with two batches in flight on two HIP streams (independent
+    # batches, as a serving loop would pipeline them); not the headline
     pipelined = None
-    if args.pipelined_probe:
+    if args.full and args.pipelined_probe:
         s2 = [stream, torch.cuda.Stream(device)]
         for i in range(max(4, args.warmup)):      # first use of a stream pays a one-off set-up (~6 ms)
             step(i, s2[i % 2].cuda_stream)
@@ -597,27 +638,29 @@ def main():
 
     ceilings = None
     shapes = None
-    if rank == 0 and not args.no_copy_ceiling:
+    if args.full and rank == 0 and not args.no_copy_ceiling:
         ceilings = stream_ceilings(torch, batches, total, stream, max(20, args.steps))
         shapes = shape_points(torch, entry, local, batches, total, nframes, stream, max(20, args.steps))
 
-    off_h, _, _ = synth_config(args.workload, rank)
-    last = batches[(args.warmup + args.steps - 1) % nb]
-    keys_h = last[2].cpu().numpy().view(np.uint32)   # this batch's own keys
-    check = verify_step(torch, nm, last, total, nframes, off_h, keys_h, stream)
-    ok_rows = gather_max(torch, [float(check["involution"] and check["keystream_all_frames"])], world, coll_dev)
-    check["ranks_verified"] = int(sum(r[0] for r in ok_rows))
-    check["all_ranks_ok"] = check["ranks_verified"] == world
+    check = None
+    if args.full:
+        off_h, _, _ = synth_config(args.workload, rank)
+        last = batches[nlast]
+        keys_h = last[2].cpu().numpy().view(np.uint32)   # this batch's own keys
+        check = verify_step(torch, nm, last, total, nframes, off_h, keys_h, stream)
+        ok_rows = gather_max(torch, [float(check["involution"] and check["keystream_all_frames"])], world, coll_dev)
+        check["ranks_verified"] = int(sum(r[0] for r in ok_rows))
+        check["all_ranks_ok"] = check["ranks_verified"] == world
 
     shards = None
-    if world > 1 and args.shard_leg:
+    if args.full and world > 1 and args.shard_leg:
         del batches, prepared
         torch.cuda.empty_cache()
         shards = shard_leg(torch, nm, entry, local, rank, world, device, stream, coll_dev, args)
 
     cpu = None
     c5 = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         del batches, prepared
         torch.cuda.empty_cache()
         if args.c5_gib > 0:
@@ -637,6 +680,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 5),
+            "full": args.full,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,

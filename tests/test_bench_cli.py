@@ -68,11 +68,37 @@ def _check_line(line, n):
 
 
 @pytest.mark.gpu
+@pytest.mark.timeout(120)
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the line carries the headline only (every secondary leg's field is null),
+    and --dump-outputs writes the last timed step's dst buffer as one float32 array of bytes:
+    here a 64 MiB batch, so the fixed-size sample."""
+    out = tmp_path / "dump"
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--rotation-bytes", str(128 << 20),
+              "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = _line(r.stdout)
+    assert line["n_gpus"] == 1 and line["steps"] == 3 and line["full"] is False
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "GiB/s" and line["dtype"] == "u8"
+    assert line["higher_is_better"] is True
+    for leg in ("verified", "c4_shards", "c5_host_to_host", "cpu_baseline", "pipelined_2stream"):
+        assert line[leg] is None, leg
+    assert line["roofline"]["ceilings"] is None and line["roofline"]["shapes"] is None
+    import numpy as np
+
+    assert sorted(p.name for p in out.iterdir()) == ["masked_payload.npy"]
+    got = np.load(out / "masked_payload.npy")
+    assert got.dtype == np.float32 and got.shape == (4 << 20,)
+    assert got.min() >= 0 and got.max() <= 255 and np.array_equal(got, np.rint(got))
+    assert np.unique(got).size == 256          # random payload XOR random keys: every byte value occurs
+
+
+@pytest.mark.gpu
 @pytest.mark.timeout(600)
 def test_bench_two_gpus_distinct_devices():
     if _gpus() < 2:
         pytest.skip("needs two GPUs")
-    r = _run(["--gpus", "2", "--steps", "5", "--warmup", "2", "--c5-gib", "0", "--cpu-seconds", "0",
+    r = _run(["--gpus", "2", "--steps", "5", "--warmup", "2", "--full", "--c5-gib", "0", "--cpu-seconds", "0",
               "--no-copy-ceiling"], timeout=540)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _line(r.stdout)
@@ -85,7 +111,7 @@ def test_bench_two_gpus_distinct_devices():
 def test_bench_launcher_rehearsal_one_gpu():
     """The child-launch path on a one-GPU box: `python bench.py --gpus 2` with both ranks on
     device 0 (the rehearsal switch only skips the device count and pins the device)."""
-    r = _run(["--gpus", "2", "--steps", "5", "--warmup", "2", "--c5-gib", "0", "--cpu-seconds", "0",
+    r = _run(["--gpus", "2", "--steps", "5", "--warmup", "2", "--full", "--c5-gib", "0", "--cpu-seconds", "0",
               "--no-copy-ceiling"], {"NETC_BENCH_DEVICE": "0", "NETC_BENCH_BACKEND": "gloo"}, timeout=540)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _line(r.stdout)

@@ -3,7 +3,7 @@
 # variant, ROUNDS times, variants interleaved so box drift hits every arm alike.  A variant is a
 # comma-separated list of VAR=value assignments ("-" = none); each run's stdout goes to
 # gpurun_out/TAG/<i>_<round>.json and its last JSON line is summarised at the end.
-#   VARIANTS="- NETC_MASK_TAPER=2097152" CMD="python -u bench.py --steps 200 --cpu-seconds 0 --c5-gib 0" \
+#   VARIANTS="- NETC_MASK_TAPER=2097152" CMD="python -u bench.py --steps 200 --full --cpu-seconds 0 --c5-gib 0" \
 #   ROUNDS=3 bash tools/gpu_ab_env.sh TAG
 set -o pipefail
 TAG=${1:-ab_env}

@@ -21,7 +21,7 @@ for s in $STEPS; do
         rc=$?
         tail -3 "$OUT/smoke.log" ;;
     bench)
-        timeout -k 10 400 python3 bench.py ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
+        timeout -k 10 400 python3 bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
         rc=$?
         cat "$OUT/bench.json"; tail -3 "$OUT/bench.err" ;;
     tests|tests/*)

@@ -5,7 +5,7 @@ set -o pipefail
 mkdir -p gpurun_out/rehearse
 for N in 2 4; do
   NETC_BENCH_DEVICE=0 NETC_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 \
-      --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --gpus $N --steps 20 \
+      --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --gpus $N --steps 20 --full \
       --warmup 5 --cpu-seconds 0 --c5-gib 0 > gpurun_out/rehearse/bench_n$N.json 2> gpurun_out/rehearse/bench_n$N.err || exit $?
   tail -1 gpurun_out/rehearse/bench_n$N.json | cut -c1-400
 done

@@ -15,5 +15,5 @@ for wl in c2 c4; do
         > "$OUT/enc_$wl.log" 2>&1 || exit $?
 done
 timeout -s KILL 120 rocprofv3 --pmc $C --kernel-include-regex "mask_np_kernel" --output-format csv -d "$OUT/mask" -o run -- \
-    python3 "$R/bench.py" --steps 10 --warmup 2 --cpu-seconds 0 --c5-gib 0 --no-copy-ceiling --no-pipelined-probe --no-shard-leg > "$OUT/mask.log" 2>&1 || exit $?
+    python3 "$R/bench.py" --steps 10 --warmup 2 --full --cpu-seconds 0 --c5-gib 0 --no-copy-ceiling --no-pipelined-probe --no-shard-leg > "$OUT/mask.log" 2>&1 || exit $?
 echo done

@@ -70,7 +70,7 @@ def main():
     hbm = 2 * statistics.mean(ft) * 1024 + statistics.mean(wt) * 1024
     out = {
         "tag": args.tag, "workload": wl, "kernel": stats.get("name"),
-        "command": "python3 bench.py --gpus 1 --steps 20 --warmup 5 --c5-gib 0 --cpu-seconds 0 "
+        "command": "python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --c5-gib 0 --cpu-seconds 0 "
                    "(the driver's bench command with the C5 and CPU legs off: the C5 leg launches the "
                    "same kernel on 512 MiB slots, which would mix into the average)",
         "rocprof_stats": stats,
