@@ -272,7 +272,13 @@ int netc_gpu_unmask_validate(int device, void* d_dst, const void* d_src, size_t 
                              const uint64_t* d_frame_offsets, const uint32_t* d_keys, const uint8_t* d_header0,
                              size_t nframes, uint8_t* d_valid, void* stream) {
     if (int r = check_device(device)) return r;
-    if (nframes == 0) return 0;
+    if (nframes == 0) {
+        // no frames, no verdicts: out of place the bytes pass through as with netc_gpu_mask_batch
+        if (d_dst == d_src) return 0;
+        DeviceGuard g(device);
+        if (g.err != hipSuccess) return fail_hip(NETC_GPU_ERUNTIME, "hipSetDevice", g.err);
+        return mask_batch_on_current(d_dst, d_src, total_bytes, d_frame_offsets, d_keys, 0, (hipStream_t)stream);
+    }
     if (!d_frame_offsets || !d_keys || !d_header0 || !d_valid) return fail(NETC_GPU_EINVAL, "null frame array");
     if (total_bytes && (!d_dst || !d_src)) return fail(NETC_GPU_EINVAL, "null payload buffer");
     if (partial_overlap(d_dst, d_src, total_bytes)) return fail(NETC_GPU_EINVAL, "dst and src partially overlap");

@@ -1196,15 +1196,17 @@ __device__ __forceinline__ void frame_edges(const uint8_t* dst, uint64_t lo, uin
     }
 }
 
-// the first 3 bytes of every window start strictly inside [lo + 3, hi) (the bytes phase A left:
-// in place another wavefront's window held the bytes before them); the 4 bytes before and
+// the first 3 bytes of every window that starts inside (lo, hi), those at or past lo + 3 (the
+// bytes phase A left: in place another wavefront's window held the bytes before them; the
+// frame's own first 3 bytes are the caller's.  A window starting 1 or 2 bytes into the frame
+// still leaves byte lo + 3, or lo + 3 and lo + 4, to this check); the 4 bytes before and
 // after each start (aligned dwords: dst - mis is 16-aligned, window starts are multiples of
 // win >= 4096) are read for 8 windows at a time, unconditionally (a start past the frame
 // re-reads the first one; a load under a per-lane branch made the compiler wait for each one
 // in turn: 29.7 us at config 4, r03k).  win 0: no seams to check.
 __device__ __forceinline__ bool seams_bad(const uint8_t* dst, uint64_t lo, uint64_t hi, uint64_t mis, uint64_t win) {
     bool bad = false;
-    const uint64_t cb0 = win ? (lo + 3 + mis + win - 1) / win * win : ~0ull;
+    const uint64_t cb0 = win ? (lo + 1 + mis + win - 1) / win * win : ~0ull;
     for (uint64_t cb = cb0; win && cb < hi + mis && !bad; cb += 8 * win) {
         uint32_t wb[8], wa[8];
 #pragma unroll
@@ -1274,7 +1276,7 @@ __global__ void utf8_messages(const uint8_t* dst, const uint64_t* off, const uin
             const uint32_t op = h0[j] & 0x0F;
             if (op >= 8) continue;                              // control frame inside the message
             if (op != 0) {
-                first = j;
+                if (!(h0[j] & 0x80)) first = j;                 // (with FIN: a finished message, orphan)
                 break;
             }
             if (h0[j] & 0x80) break;                            // a finished message: orphan continuation

@@ -16,16 +16,22 @@ the same vector_* sequence against both implementations and must print the same.
 Skipped where /root/reference is absent (the GPU box): nothing here reads it at run time there.
 """
 
+import hashlib
 import os
 import re
 import subprocess
+import tempfile
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
 ORACLE = os.path.join(ROOT, "oracle")
-DROPIN_DIR = "/tmp/netc_dropin"   # oracle/Makefile DROPIN_DIR: outside the repository
+# oracle/Makefile DROPIN_DIR: outside the repository, and this user's and this checkout's own --
+# the libnetc binary carries the checkout's library path, so another checkout's (or another
+# user's, which this one could not overwrite) must never be taken for up to date
+DROPIN_DIR = os.path.join(tempfile.gettempdir(), "netc_dropin_%d_%s" % (os.getuid(),
+                                                                        hashlib.sha1(ROOT.encode()).hexdigest()[:12]))
 LIBNETC = os.path.join(ROOT, "netc_amd", "lib", "libnetc.so")
 
 pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "tests", "ws", "test001.c")),
@@ -39,7 +45,8 @@ CHECKS = ["on_connect_server", "send_basic_server", "send_multiple_frames_server
 
 @pytest.fixture(scope="module")
 def built():
-    subprocess.run(["make", "-C", ORACLE, "dropin"], check=True, capture_output=True, text=True)
+    subprocess.run(["make", "-C", ORACLE, "dropin", f"DROPIN_DIR={DROPIN_DIR}"], check=True, capture_output=True,
+                   text=True)
     return {k: os.path.join(DROPIN_DIR, f"ws_test001_{k}") for k in ("reference", "libnetc")}
 
 

@@ -11,6 +11,7 @@ import pytest
 
 from netc_amd import mask as nm
 from oracle import oracle as orc
+from tests.scanutil import ScanOutputs
 
 pytestmark = pytest.mark.gpu
 
@@ -30,23 +31,10 @@ def run_scan(torch, wire: np.ndarray, start=0, strict=True, max_frames=None, par
     cap = n if max_frames is None else max_frames
     w = torch.from_numpy(np.ascontiguousarray(wire)).cuda() if wire.size else torch.zeros(1, dtype=torch.uint8,
                                                                                           device="cuda")
-    hdr = torch.full((cap + 1,), -7, dtype=torch.int64, device="cuda")
-    keys = torch.zeros(max(cap, 1), dtype=torch.int32, device="cuda")
-    b0 = torch.zeros(max(cap, 1), dtype=torch.uint8, device="cuda")
-    res = torch.full((3,), -7, dtype=torch.int64, device="cuda")
-    nm.scan_frames(w, hdr, keys, b0, res, start=start, strict=strict, length=wire.size)
+    outs = ScanOutputs(torch, cap)   # slices of sentinel-filled tensors: a write past the capacity is seen
+    nm.scan_frames(w, outs.hdr, outs.keys, outs.b0, outs.res, start=start, strict=strict, length=wire.size)
     torch.cuda.synchronize()
-    r = res.cpu().numpy().view(np.uint64)
-    assert int(r[0]) == n, f"frames {int(r[0])} != {n}"
-    assert int(r[1]) == exp_consumed, f"consumed {int(r[1])} != {exp_consumed}"
-    assert (None if int(r[2]) == (1 << 64) - 1 else int(r[2])) == exp_err
-    k = min(n, cap)
-    got_hdr = hdr.cpu().numpy().view(np.uint64)
-    assert np.array_equal(got_hdr[:k], exp_hdr[:k]), f"header offsets differ at {np.nonzero(got_hdr[:k] != exp_hdr[:k])[0][:4]}"
-    assert np.array_equal(keys.cpu().numpy().view(np.uint32)[:k], exp_keys[:k])
-    assert np.array_equal(b0.cpu().numpy()[:k], exp_b0[:k])
-    if n <= cap:
-        assert int(got_hdr[n]) == exp_consumed
+    outs.check_scan(exp_hdr, exp_keys, exp_b0, exp_consumed, exp_err)
     if parallel:
         why = nm.scan_diag()
         assert why == 0, f"serial fallback, reason {why:#x}"
@@ -160,11 +148,13 @@ def test_header_byte_variants(torch_cuda):
     assert run_scan(torch_cuda, wire, parallel=True) == 500
 
 
-def test_max_frames_cap(torch_cuda):
+def test_max_frames_cap(torch_cuda, gpu_knob):
     rng = np.random.default_rng(11)
     wire, _ = _stream(rng, rng.integers(0, 2000, 400))
-    run_scan(torch_cuda, wire, max_frames=100, parallel=True)
-    run_scan(torch_cuda, wire, max_frames=0, parallel=True)
+    for onepass in (None, "0", "1"):   # the default choice, the graph path, the one-pass path
+        gpu_knob("SCAN_ONEPASS", onepass)
+        for cap in (100, 0, 1, 399):   # (the guarded outputs of run_scan show a write past the cap)
+            run_scan(torch_cuda, wire, max_frames=cap, parallel=True)
 
 
 def test_scratch_left_clean_between_calls(torch_cuda):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
+from tests.utf8util import MESSAGE_STRUCTURE, batch_arrays, sweep_frames
 
 KAT = [
     (b"", True), (b"plain ascii {json: 1}", True), (b"\x00\x7f", True),
@@ -79,3 +80,36 @@ def test_batch_verdicts_follow_messages():
     h = np.array([b for b, _ in frames], dtype=np.uint8)
     v = orc.validate_batch(payload, off, h)
     assert list(v) == [1, 1, 1, 0, 1, 1, 1, 1, 0]
+    # orphan continuations, abandoned and unfinished messages, reserved opcodes, RSV bits, empty
+    # continuation frames, control frames inside a message: the hand-written verdicts the kernel
+    # is held to (tests/test_gpu_utf8.py::test_message_structure_known_answers)
+    for frames, expect in MESSAGE_STRUCTURE:
+        assert len(frames) == len(expect)
+        v = orc.validate_batch(*batch_arrays(frames))
+        assert list(v) == expect, [(hex(h), p) for h, p in frames]
+
+
+@pytest.mark.parametrize("layout", ["bare", "padded"])
+def test_agrees_with_cpython_on_every_sequence_prefix(layout):
+    # all 1,048,576 four-byte sequences of tests/utf8util.sweep_sequences, alone and between
+    # ASCII: the set the kernel's two copies of the rule are swept with
+    frames = np.ascontiguousarray(sweep_frames(layout))
+    n, w = frames.shape
+    assert n == 1 << 20
+    raw = frames.tobytes()
+    fn, base = orc.lib().oracle_utf8_valid, frames.ctypes.data
+    valid = 0
+    for i in range(n):
+        o = i * w
+        try:
+            raw[o:o + w].decode("utf-8", errors="strict")
+            ok = 1
+        except UnicodeDecodeError:
+            ok = 0
+        if fn(base + o, w) != ok:
+            raise AssertionError(f"oracle_utf8_valid({raw[o:o + w].hex()}) != {ok}")
+        valid += ok
+    assert 0 < valid < n
+    # and through the binding the GPU tests call, on a sample
+    for i in range(0, n, 4099):
+        assert orc.utf8_valid(frames[i]) == _py_valid(raw[i * w:(i + 1) * w])
