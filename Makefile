@@ -19,8 +19,8 @@ HIPFLAGS   ?= -O3 -g -fPIC -std=c++17 --offload-arch=$(ARCH) -Wall -Wno-unused-r
 HOST_SRCS  := $(wildcard netc_amd/csrc/host/*.c)
 HOST_HDRS  := $(wildcard include/*.h include/*/*.h)
 GPU_SRCS   := netc_amd/csrc/ws_mask_gpu.hip netc_amd/csrc/ws_frame_gpu.hip netc_amd/csrc/ws_scan_gpu.hip netc_amd/csrc/ws_ingest.hip netc_amd/csrc/ws_egress.hip \
-              netc_amd/csrc/ws_mask_api.hip netc_amd/csrc/ws_hub.hip netc_amd/csrc/ws_egress_hub.hip
-GPU_HDRS   := netc_amd/csrc/ws_mask_gpu.h netc_amd/csrc/gpu_util.h include/ws/mask.h include/ws/frame.h include/ws/ingest.h \
+              netc_amd/csrc/ws_mask_api.hip netc_amd/csrc/ws_hub.hip netc_amd/csrc/ws_egress_hub.hip netc_amd/csrc/ws_decode_gpu.hip
+GPU_HDRS   := netc_amd/csrc/ws_mask_gpu.h netc_amd/csrc/gpu_util.h netc_amd/csrc/ws_decode_gpu.h include/ws/mask.h include/ws/frame.h include/ws/ingest.h \
               include/ws/route.h include/ws/common.h include/ws/egress.h include/ws/hub.h include/ws/egress_hub.h
 
 .PHONY: all host gpu oracle diag clean asan mock

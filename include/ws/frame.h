@@ -138,7 +138,7 @@ int netc_gpu_scan_frames(int device, const void *d_wire, size_t len, uint64_t st
                          uint32_t *d_keys, uint8_t *d_b0, size_t max_frames, uint64_t *d_result, void *stream);
 
 /** Same as netc_gpu_stream_release (include/ws/mask.h): frees ALL scratch kept for
- *  (device, stream) -- scan, assembly, UTF-8 flags; waits for that stream first.  0 or a code. */
+ *  (device, stream) -- scan, assembly, decode, UTF-8 flags; waits for that stream first.  0 or a code. */
 int netc_gpu_scan_release(int device, void *stream);
 
 /**
@@ -176,6 +176,55 @@ int netc_ws_scan_frames_host(const void *wire, size_t len, uint64_t start, int f
  */
 int netc_gpu_unmask_frames(int device, void *d_wire, size_t len, const uint64_t *d_hdr, const uint32_t *d_keys,
                            size_t max_frames, const uint64_t *d_result, void *stream);
+
+/** d_dresult layout of netc_gpu_decode_frames. */
+#define NETC_WS_DECODE_FRAMES   0   /* frames decoded: n = min(frames the scan found, max_frames) */
+#define NETC_WS_DECODE_BYTES    1   /* payload bytes written = d_offsets[n]                       */
+#define NETC_WS_DECODE_MESSAGES 2   /* complete messages M among those n frames                   */
+
+/**
+ * The inverse of netc_gpu_encode_frames: the frames a netc_gpu_scan_frames call found in d_wire
+ * as a batch in the layout of include/ws/mask.h, plus a message table, out of place on `device`.
+ *   d_payload         device output, payload_capacity >= len bytes, not overlapping d_wire:
+ *                     frame k's payload, unmasked from phase 0 with d_keys[k] (key 0, MASK clear:
+ *                     copied), at [d_offsets[k], d_offsets[k+1]); payloads back to back, unpadded
+ *   d_offsets         device output, n + 1 uint64 (max_frames + 1 entries are enough); [0] = 0
+ *   d_msg_first       device output, M + 1 uint64 (max_frames + 1 are enough), or NULL with
+ *   d_msg_opcode      device output, M bytes (max_frames are enough), or NULL: message m is the
+ *                     frames [d_msg_first[m], d_msg_first[m+1]) -- the run up to and including the
+ *                     next frame with FIN, ws_parse_frame's rule (src/ws/common.c:303-347), so a
+ *                     control frame between two fragments belongs to the message around it
+ *                     (include/ws/ingest.h) -- and its bytes d_payload[d_offsets[d_msg_first[m]],
+ *                     d_offsets[d_msg_first[m+1]]).  d_msg_opcode[m] is the last non-zero opcode
+ *                     among its frames (:163-164), 0 if there is none.  d_msg_first[M] is the
+ *                     first frame of the message still open, or n.
+ *   d_dresult         device output, 3 uint64 (NETC_WS_DECODE_*)
+ *   d_hdr, d_keys, d_b0, max_frames, d_result
+ *                     that scan's outputs, read on the device: queue this on the same stream
+ *                     right after the scan, no synchronisation needed (as netc_gpu_unmask_frames;
+ *                     d_wire is left as it is, so both may run).  Frames beyond max_frames are
+ *                     not decoded.
+ * Nothing but d_payload[0, BYTES), d_offsets[0, n], d_msg_first[0, M], d_msg_opcode[0, M) and
+ * d_dresult[0, 3) is written.  len == 0 or no frame: d_offsets[0] = d_msg_first[0] = 0 and a zero
+ * result.  NETC_GPU_EINVAL: a null required pointer, payload_capacity < len (a stream's payload is
+ * shorter than the stream, so nothing is checked on the device), d_payload overlapping d_wire,
+ * exactly one of the message arrays NULL.  Asynchronous on `stream`; scratch per (device, stream)
+ * as the scan's, freed by netc_gpu_stream_release.
+ */
+int netc_gpu_decode_frames(int device, void *d_payload, size_t payload_capacity, uint64_t *d_offsets,
+                           uint64_t *d_msg_first, uint8_t *d_msg_opcode, uint64_t *d_dresult, const void *d_wire,
+                           size_t len, const uint64_t *d_hdr, const uint32_t *d_keys, const uint8_t *d_b0,
+                           size_t max_frames, const uint64_t *d_result, void *stream);
+
+/**
+ * The same decode over host memory, on the calling thread (libnetc.so): a serial walk over the
+ * recorded frames with netc_ws_mask.  Arguments, outputs, write bounds and NETC_GPU_EINVAL cases
+ * as netc_gpu_decode_frames, all pointers host memory.  Returns 0 or NETC_GPU_EINVAL.
+ */
+int netc_ws_decode_frames_host(void *payload, size_t payload_capacity, uint64_t *offsets, uint64_t *msg_first,
+                               uint8_t *msg_opcode, uint64_t *dresult, const void *wire, size_t len,
+                               const uint64_t *hdr, const uint32_t *keys, const uint8_t *b0, size_t max_frames,
+                               const uint64_t *result);
 
 #ifdef __cplusplus
 }

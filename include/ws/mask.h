@@ -187,7 +187,8 @@ int netc_gpu_knob(int knob, int64_t value);
 /**
  * Free every piece of scratch this library keeps for (device, stream): the frame
  * scan's (netc_gpu_scan_frames, include/ws/frame.h), the frame assembly's
- * (netc_gpu_encode_frames) and the UTF-8 flags of netc_gpu_unmask_validate.  It
+ * (netc_gpu_encode_frames), the frame decode's (netc_gpu_decode_frames: the status
+ * words of its offsets scan) and the UTF-8 flags of netc_gpu_unmask_validate.  It
  * synchronises the stream first.  Call it before destroying a stream those entries
  * ran on; a later call on the stream allocates afresh.  netc_gpu_scan_release is
  * the same call under its round-1 name.

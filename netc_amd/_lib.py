@@ -64,6 +64,9 @@ def host() -> ctypes.CDLL:
                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                                      ctypes.c_void_p]
             lib.netc_ws_scan_frames_host.restype = ctypes.c_int
+            lib.netc_ws_decode_frames_host.argtypes = [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 5 + \
+                [ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p]
+            lib.netc_ws_decode_frames_host.restype = ctypes.c_int
             _host = lib
         return _host
 
@@ -126,6 +129,9 @@ def gpu() -> ctypes.CDLL:
             lib.netc_gpu_scan_diag.restype = ctypes.c_int64
             lib.netc_gpu_unmask_frames.argtypes = [ctypes.c_int, vp, ctypes.c_size_t, vp, vp, ctypes.c_size_t, vp, vp]
             lib.netc_gpu_unmask_frames.restype = ctypes.c_int
+            lib.netc_gpu_decode_frames.argtypes = [ctypes.c_int, vp, ctypes.c_size_t, vp, vp, vp, vp, vp, ctypes.c_size_t,
+                                                   vp, vp, vp, ctypes.c_size_t, vp, vp]
+            lib.netc_gpu_decode_frames.restype = ctypes.c_int
             lib.netc_gpu_unmask_validate.argtypes = [ctypes.c_int, vp, vp, ctypes.c_size_t, vp, vp, vp,
                                                      ctypes.c_size_t, vp, vp]
             lib.netc_gpu_unmask_validate.restype = ctypes.c_int

@@ -14,6 +14,7 @@
 #include <utility>
 #include <vector>
 
+#include "ws_decode_gpu.h"
 #include "ws_mask_gpu.h"
 
 extern "C" {
@@ -425,6 +426,7 @@ int netc_gpu_stream_release(int device, void* stream) {
     (void)netc_gpu::release_stream_scratch(device, (hipStream_t)stream);   // frame scan
     (void)netc_gpu::release_enc_scratch(device, (hipStream_t)stream);      // frame assembly
     (void)validate_scratch_release(device, (hipStream_t)stream);           // UTF-8 flags
+    (void)netc_gpu::release_dec_scratch(device, (hipStream_t)stream);      // frame decode
     return 0;
 }
 
@@ -450,6 +452,31 @@ int netc_gpu_unmask_frames(int device, void* d_wire, size_t len, const uint64_t*
     hipError_t e = netc_gpu::launch_unmask_scanned((uint8_t*)d_wire, len, d_hdr, d_keys, max_frames, d_result,
                                                    (hipStream_t)stream, cfg_now());
     if (e != hipSuccess) return fail_hip(NETC_GPU_ELAUNCH, "unmask launch", e);
+    return 0;
+}
+
+int netc_gpu_decode_frames(int device, void* d_payload, size_t payload_capacity, uint64_t* d_offsets,
+                           uint64_t* d_msg_first, uint8_t* d_msg_opcode, uint64_t* d_dresult, const void* d_wire,
+                           size_t len, const uint64_t* d_hdr, const uint32_t* d_keys, const uint8_t* d_b0,
+                           size_t max_frames, const uint64_t* d_result, void* stream) {
+    if (int r = check_device(device)) return r;
+    if (!d_offsets || !d_dresult) return fail(NETC_GPU_EINVAL, "null decode output");
+    if (!d_hdr || !d_result || (max_frames && (!d_keys || !d_b0))) return fail(NETC_GPU_EINVAL, "null scan output");
+    if ((d_msg_first == nullptr) != (d_msg_opcode == nullptr))
+        return fail(NETC_GPU_EINVAL, "message table: d_msg_first and d_msg_opcode must both be set or both be null");
+    if (len && (!d_wire || !d_payload)) return fail(NETC_GPU_EINVAL, "null stream or payload buffer");
+    if (payload_capacity < len)
+        return fail(NETC_GPU_EINVAL, "payload capacity %zu is below the stream length %zu", payload_capacity, len);
+    if (len >= (1ull << 40)) return fail(NETC_GPU_EINVAL, "stream too long");
+    if (ranges_overlap(d_payload, payload_capacity, d_wire, len))
+        return fail(NETC_GPU_EINVAL, "payload and wire overlap (the decode is out of place)");
+    DeviceGuard g(device);
+    if (g.err != hipSuccess) return fail_hip(NETC_GPU_ERUNTIME, "hipSetDevice", g.err);
+    hipError_t e = netc_gpu::launch_decode_frames((uint8_t*)d_payload, d_offsets, d_msg_first, d_msg_opcode, d_dresult,
+                                                  (const uint8_t*)d_wire, len, d_hdr, d_keys, d_b0, max_frames,
+                                                  d_result, (hipStream_t)stream);
+    if (e == hipErrorOutOfMemory) return fail_hip(NETC_GPU_ENOMEM, "frame decode scratch", e);
+    if (e != hipSuccess) return fail_hip(NETC_GPU_ELAUNCH, "frame decode launch", e);
     return 0;
 }
 

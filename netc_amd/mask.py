@@ -134,7 +134,7 @@ def knob(name: str, value):
 
 def stream_release(stream=None, device: int = 0) -> None:
     """netc_gpu_stream_release: synchronise `stream`, then free every scratch array the library
-    keeps for it (scan, frame assembly, UTF-8 flags)."""
+    keeps for it (scan, frame assembly, frame decode, UTF-8 flags)."""
     _check(_lib.gpu().netc_gpu_stream_release(device, _stream_handle(stream)))
 
 
@@ -348,6 +348,88 @@ def unmask_frames(wire, hdr, keys, result, length: Optional[int] = None, stream=
     dev = wire.device.index if device is None else device
     _check(_lib.gpu().netc_gpu_unmask_frames(dev, wire.data_ptr(), n, hdr.data_ptr(), keys.data_ptr(),
                                              hdr.numel() - 1, result.data_ptr(), _stream_handle(stream)))
+
+
+NETC_WS_DECODE_FRAMES, NETC_WS_DECODE_BYTES, NETC_WS_DECODE_MESSAGES = 0, 1, 2
+
+
+def decode_frames(payload, offsets, msg_first, msg_opcode, dresult, wire, hdr, keys, b0, result,
+                  length: Optional[int] = None, stream=None, device: Optional[int] = None) -> None:
+    """netc_gpu_decode_frames: the frames scan_frames found in `wire` as a batch (device tensors).
+
+    payload: uint8, >= length bytes (output, not overlapping wire); offsets: int64, max_frames + 1
+    (output); msg_first: int64, max_frames + 1 and msg_opcode: uint8, max_frames (outputs, or both
+    None); dresult: int64 (3) receives [frames decoded, payload bytes, complete messages].
+    hdr / keys / b0 / result are the scan's outputs, read on the device: queue this right after
+    scan_frames on the same stream.  The C entry checks capacity, overlap and the message pair.
+    """
+    import torch
+
+    n = wire.numel() if length is None else int(length)
+    max_frames = hdr.numel() - 1
+    for name, t, dt in (("payload", payload, (torch.uint8,)), ("wire", wire, (torch.uint8,)),
+                        ("offsets", offsets, (torch.int64, torch.uint64)),
+                        ("dresult", dresult, (torch.int64, torch.uint64)),
+                        ("msg_first", msg_first, (torch.int64, torch.uint64)), ("msg_opcode", msg_opcode, (torch.uint8,))):
+        if t is None and name.startswith("msg_"):
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous device tensor")
+        if t.dtype not in dt:
+            raise TypeError(f"{name} must be {dt[0]}")
+    if n > wire.numel():
+        raise ValueError("length past the wire tensor")
+    if offsets.numel() < max_frames + 1 or dresult.numel() < 3 or keys.numel() < max_frames or b0.numel() < max_frames:
+        raise ValueError("output or scan tensors too small for max_frames")
+    if msg_first is not None and msg_first.numel() < max_frames + 1:
+        raise ValueError("msg_first must have max_frames + 1 entries")
+    if msg_opcode is not None and msg_opcode.numel() < max_frames:
+        raise ValueError("msg_opcode must have max_frames entries")
+    dev = wire.device.index if device is None else device
+    _check(_lib.gpu().netc_gpu_decode_frames(dev, payload.data_ptr(), payload.numel(), offsets.data_ptr(),
+                                             0 if msg_first is None else msg_first.data_ptr(),
+                                             0 if msg_opcode is None else msg_opcode.data_ptr(), dresult.data_ptr(),
+                                             wire.data_ptr(), n, hdr.data_ptr(), keys.data_ptr(), b0.data_ptr(),
+                                             max_frames, result.data_ptr(), _stream_handle(stream)))
+
+
+def decode_frames_host(wire: np.ndarray, hdr: np.ndarray, keys: np.ndarray, b0: np.ndarray, result: np.ndarray,
+                       length: Optional[int] = None, max_frames: Optional[int] = None, messages: bool = True):
+    """netc_ws_decode_frames_host (libnetc.so): the same decode over host arrays, on this thread.
+
+    hdr / keys / b0 / result as scan_frames_host returns them (max_frames defaults to hdr.size - 1).
+    Returns (payload uint8 [bytes], offsets uint64 [n + 1], msg_first uint64 [M + 1], msg_opcode
+    uint8 [M], dresult uint64 [3]); msg_first and msg_opcode are None with messages=False.
+    """
+    w = np.ascontiguousarray(wire, dtype=np.uint8)
+    n = w.size if length is None else int(length)
+    if n > w.size:
+        raise ValueError("length past the array")
+    h = np.ascontiguousarray(hdr, dtype=np.uint64)
+    cap = h.size - 1 if max_frames is None else int(max_frames)
+    if cap < 0 or h.size < cap + 1:
+        raise ValueError("hdr must have max_frames + 1 entries")
+    k = np.ascontiguousarray(keys, dtype=np.uint32)
+    b = np.ascontiguousarray(b0, dtype=np.uint8)
+    r = np.ascontiguousarray(result, dtype=np.uint64)
+    if k.size < cap or b.size < cap or r.size < 3:
+        raise ValueError("keys / b0 need max_frames entries, result 3")
+    payload = np.zeros(max(n, 1), np.uint8)
+    offsets = np.zeros(cap + 1, np.uint64)
+    first = np.zeros(cap + 1, np.uint64) if messages else None
+    opcode = np.zeros(max(cap, 1), np.uint8) if messages else None
+    dres = np.zeros(3, np.uint64)
+    rc = _lib.host().netc_ws_decode_frames_host(payload.ctypes.data, n, offsets.ctypes.data,
+                                                first.ctypes.data if messages else None,
+                                                opcode.ctypes.data if messages else None, dres.ctypes.data,
+                                                w.ctypes.data if w.size else None, n, h.ctypes.data,
+                                                k.ctypes.data if k.size else None, b.ctypes.data if b.size else None,
+                                                cap, r.ctypes.data)
+    if rc != 0:
+        raise NetcGpuError(rc, "netc_ws_decode_frames_host: invalid arguments")
+    nf, nb, nm_ = int(dres[0]), int(dres[1]), int(dres[2])
+    return (payload[:nb], offsets[:nf + 1], first[:nm_ + 1] if messages else None,
+            opcode[:nm_] if messages else None, dres)
 
 
 def mask_stream_host(dst: np.ndarray, src: np.ndarray, offsets: np.ndarray, keys: np.ndarray,
