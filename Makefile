@@ -17,17 +17,18 @@ CFLAGS     ?= -O3 -g -Wall -Wextra -Wno-unused-parameter -fPIC -std=gnu11 -fvisi
 HIPFLAGS   ?= -O3 -g -fPIC -std=c++17 --offload-arch=$(ARCH) -Wall -Wno-unused-result
 
 HOST_SRCS  := $(wildcard netc_amd/csrc/host/*.c)
-HOST_HDRS  := $(wildcard include/*.h include/*/*.h)
+HOST_HDRS  := $(wildcard include/*.h include/*/*.h) netc_amd/csrc/host/ws_header.h
 GPU_SRCS   := netc_amd/csrc/ws_mask_gpu.hip netc_amd/csrc/ws_frame_gpu.hip netc_amd/csrc/ws_scan_gpu.hip netc_amd/csrc/ws_ingest.hip netc_amd/csrc/ws_egress.hip \
               netc_amd/csrc/ws_mask_api.hip netc_amd/csrc/ws_hub.hip netc_amd/csrc/ws_egress_hub.hip netc_amd/csrc/ws_decode_gpu.hip
-GPU_HDRS   := netc_amd/csrc/ws_mask_gpu.h netc_amd/csrc/gpu_util.h netc_amd/csrc/ws_decode_gpu.h include/ws/mask.h include/ws/frame.h include/ws/ingest.h \
+RING_HDRS  := netc_amd/csrc/ws_ring_host.h netc_amd/csrc/host/ws_header.h
+GPU_HDRS   := netc_amd/csrc/ws_mask_gpu.h netc_amd/csrc/gpu_util.h netc_amd/csrc/ws_decode_gpu.h $(RING_HDRS) include/ws/mask.h include/ws/frame.h include/ws/ingest.h \
               include/ws/route.h include/ws/common.h include/ws/egress.h include/ws/hub.h include/ws/egress_hub.h
 
 .PHONY: all host gpu oracle diag clean asan mock
 all: host gpu oracle mock
 mock: tests/bin/libnetc_ingest_mock.so tests/bin/ws_close_track_mock tests/bin/libnetc_hub_cpu.so tests/bin/ws_hub_server_cpu \
       tests/bin/ws_egress_hub_server_cpu tests/bin/ws_echo_server_cpu
-host: $(LIBDIR)/libnetc.so tests/bin/ws_route_lookup
+host: $(LIBDIR)/libnetc.so tests/bin/ws_route_lookup tests/bin/libws_header_shim.so
 gpu: $(LIBDIR)/libnetc_ws_gpu.so $(LIBDIR)/libnetc_ceiling.so tests/bin/ws_gpu_epoll tests/bin/ws_egress_bench \
      tests/bin/ws_route_bench tests/bin/ws_hub_server tests/bin/ws_egress_hub_server tests/bin/ws_echo_server \
      tests/bin/ws_close_track
@@ -50,57 +51,23 @@ $(LIBDIR)/libnetc_ceiling.so: netc_amd/csrc/ceiling.hip
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
 
-# the GPU receive route under netc's caller contract (tests/test_gpu_epoll.py): a C program,
-# epoll + TCP loopback, linked against both libraries as a netc server would be
-tests/bin/ws_gpu_epoll: tests/drivers/ws_gpu_epoll.c $(LIBDIR)/libnetc_ws_gpu.so $(LIBDIR)/libnetc.so $(HOST_HDRS)
-	@mkdir -p tests/bin
-	$(CC) -O2 -g -Wall -std=gnu11 -Iinclude -o $@ $< -L$(LIBDIR) -lnetc_ws_gpu -lnetc -L/opt/rocm/lib -lamdhip64 \
-	    -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib -lpthread -ldl
-
-# send rates of the GPU egress ring beside the CPU ws_send_message (tools/bench_egress.py)
-tests/bin/ws_egress_bench: tests/drivers/ws_egress_bench.c $(LIBDIR)/libnetc_ws_gpu.so $(LIBDIR)/libnetc.so $(HOST_HDRS)
-	@mkdir -p tests/bin
-	$(CC) -O2 -g -Wall -std=gnu11 -Iinclude -o $@ $< -L$(LIBDIR) -lnetc_ws_gpu -lnetc -L/opt/rocm/lib -lamdhip64 \
-	    -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib -lpthread -ldl
-
-# receive rates through ws_parse_frame over loopback TCP, netc's once-per-event loop: CPU path, GPU
-# route, the reference's own parser (tools/bench_routes.py)
-tests/bin/ws_route_bench: tests/drivers/ws_route_bench.c $(LIBDIR)/libnetc_ws_gpu.so $(LIBDIR)/libnetc.so $(HOST_HDRS)
-	@mkdir -p tests/bin
-	$(CC) -O2 -g -Wall -std=gnu11 -Iinclude -o $@ $< -L$(LIBDIR) -lnetc_ws_gpu -lnetc -L/opt/rocm/lib -lamdhip64 \
-	    -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib -lpthread -ldl
-
-# TEST ONLY: the ring's host code (ws_ingest.hip) over a host-memory mock of the HIP runtime
-# (tests/mockhip), so tests/test_route_mock.py drives the ingest ring and the ws_parse_frame route
-# on a machine without a GPU.  Never loaded by the product.
-tests/bin/libnetc_ingest_mock.so: netc_amd/csrc/ws_ingest.hip netc_amd/csrc/ws_hub.hip netc_amd/csrc/ws_egress_hub.hip tests/mockhip/mock_gpu.cc tests/mockhip/hip/hip_runtime.h \
-                                  netc_amd/csrc/ws_mask_gpu.h $(LIBDIR)/libnetc.so $(HOST_HDRS)
-	@mkdir -p tests/bin
-	g++ -O1 -g -std=c++17 -fPIC -shared -Wall -Wno-unused-result -Itests/mockhip -x c++ netc_amd/csrc/ws_ingest.hip netc_amd/csrc/ws_hub.hip netc_amd/csrc/ws_egress_hub.hip \
-	    -x none tests/mockhip/mock_gpu.cc -L$(LIBDIR) -lnetc -Wl,-Bsymbolic -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)' -o $@
-
-# many connections on one event loop, one GPU hub (tests/test_gpu_hub.py, tools/bench_hub.py)
-tests/bin/ws_hub_server: tests/drivers/ws_hub_server.c $(LIBDIR)/libnetc_ws_gpu.so $(LIBDIR)/libnetc.so $(HOST_HDRS)
-	@mkdir -p tests/bin
-	$(CC) -O2 -g -Wall -std=gnu11 -Iinclude -o $@ $< -L$(LIBDIR) -lnetc_ws_gpu -lnetc -L/opt/rocm/lib -lamdhip64 \
-	    -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib -lpthread -ldl
-
-# an echo server in netc's shape, GPU both ways (receive hub in, egress hub out)
-tests/bin/ws_echo_server: tests/drivers/ws_echo_server.c $(LIBDIR)/libnetc_ws_gpu.so $(LIBDIR)/libnetc.so $(HOST_HDRS)
-	@mkdir -p tests/bin
-	$(CC) -O2 -g -Wall -std=gnu11 -Iinclude -o $@ $< -L$(LIBDIR) -lnetc_ws_gpu -lnetc -L/opt/rocm/lib -lamdhip64 \
-	    -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib -lpthread -ldl
-
-# the send side: many connections answered from one loop through one GPU egress hub
-# (tests/test_gpu_egress_hub.py, tools/bench_hub.py --send)
-tests/bin/ws_egress_hub_server: tests/drivers/ws_egress_hub_server.c $(LIBDIR)/libnetc_ws_gpu.so $(LIBDIR)/libnetc.so $(HOST_HDRS)
-	@mkdir -p tests/bin
-	$(CC) -O2 -g -Wall -std=gnu11 -Iinclude -o $@ $< -L$(LIBDIR) -lnetc_ws_gpu -lnetc -L/opt/rocm/lib -lamdhip64 \
-	    -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib -lpthread -ldl
-
-# close() on routed sockets in a process linked as netc links libnetc.so (tests/test_close_track.py):
-# against the GPU library, and against the mock (CPU suite)
-tests/bin/ws_close_track: tests/drivers/ws_close_track.c $(LIBDIR)/libnetc_ws_gpu.so $(LIBDIR)/libnetc.so $(HOST_HDRS)
+# C drivers linked against both libraries as a netc server would be:
+#   ws_gpu_epoll          the GPU receive route under netc's caller contract, epoll + TCP loopback
+#                         (tests/test_gpu_epoll.py)
+#   ws_egress_bench       send rates of the GPU egress ring beside the CPU ws_send_message
+#                         (tools/bench_egress.py)
+#   ws_route_bench        receive rates through ws_parse_frame over loopback TCP, netc's once-per-event
+#                         loop: CPU path, GPU route, the reference's own parser (tools/bench_routes.py)
+#   ws_hub_server         many connections on one event loop, one GPU hub (tests/test_gpu_hub.py,
+#                         tools/bench_hub.py)
+#   ws_echo_server        an echo server in netc's shape, GPU both ways (receive hub in, egress hub out)
+#   ws_egress_hub_server  the send side: many connections answered from one loop through one GPU
+#                         egress hub (tests/test_gpu_egress_hub.py, tools/bench_hub.py --send)
+#   ws_close_track        close() on routed sockets in a process linked as netc links libnetc.so
+#                         (tests/test_close_track.py): against the GPU library, and (_mock) the CPU suite's
+GPU_DRIVERS := ws_gpu_epoll ws_egress_bench ws_route_bench ws_hub_server ws_echo_server ws_egress_hub_server \
+               ws_close_track
+$(GPU_DRIVERS:%=tests/bin/%): tests/bin/%: tests/drivers/%.c $(LIBDIR)/libnetc_ws_gpu.so $(LIBDIR)/libnetc.so $(HOST_HDRS)
 	@mkdir -p tests/bin
 	$(CC) -O2 -g -Wall -std=gnu11 -Iinclude -o $@ $< -L$(LIBDIR) -lnetc_ws_gpu -lnetc -L/opt/rocm/lib -lamdhip64 \
 	    -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib -lpthread -ldl
@@ -108,18 +75,30 @@ tests/bin/ws_close_track_mock: tests/drivers/ws_close_track.c tests/bin/libnetc_
 	$(CC) -O2 -g -Wall -std=gnu11 -Iinclude -o $@ $< -Ltests/bin -lnetc_ingest_mock -L$(LIBDIR) -lnetc \
 	    -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)' -lpthread -ldl
 
-# MEASUREMENT CONTROL ONLY ("hubcpu" legs of tools/bench_hub.py): the hubs' and rings' host code with
-# the device work done on the host (tests/mockhip; netc_ws_mask for the XOR, libnetc's header walk),
-# at -O3, and the server drivers linked to it -- the same batching and syscalls as the GPU legs, so
-# the difference between "hub" and "hubcpu" is what the GPU itself adds or costs.  Never the product.
-tests/bin/libnetc_hub_cpu.so: netc_amd/csrc/ws_ingest.hip netc_amd/csrc/ws_hub.hip netc_amd/csrc/ws_egress_hub.hip tests/mockhip/mock_gpu.cc \
-                              tests/mockhip/hip/hip_runtime.h netc_amd/csrc/ws_mask_gpu.h $(LIBDIR)/libnetc.so $(HOST_HDRS)
+# The rings' and hubs' host code (ws_ingest.hip, ws_hub.hip, ws_egress_hub.hip) compiled by g++ over a
+# host-memory mock of the HIP runtime (tests/mockhip), twice.  Never loaded by the product.
+#   libnetc_ingest_mock.so  TEST ONLY (-O1): tests/test_route_mock.py drives the ingest ring, the hubs
+#                           and the ws_parse_frame route on a machine without a GPU
+#   libnetc_hub_cpu.so      MEASUREMENT CONTROL ONLY (-O3; "hubcpu" legs of tools/bench_hub.py): the device
+#                           work done on the host (netc_ws_mask for the XOR, libnetc's header walk), and the
+#                           server drivers linked to it -- the same batching and syscalls as the GPU legs,
+#                           so the difference between "hub" and "hubcpu" is what the GPU itself adds or costs
+MOCK_SRCS := netc_amd/csrc/ws_ingest.hip netc_amd/csrc/ws_hub.hip netc_amd/csrc/ws_egress_hub.hip
+tests/bin/libnetc_ingest_mock.so: MOCK_OPT := -O1
+tests/bin/libnetc_hub_cpu.so: MOCK_OPT := -O3
+tests/bin/libnetc_ingest_mock.so tests/bin/libnetc_hub_cpu.so: $(MOCK_SRCS) tests/mockhip/mock_gpu.cc tests/mockhip/hip/hip_runtime.h \
+                              netc_amd/csrc/ws_mask_gpu.h $(RING_HDRS) $(LIBDIR)/libnetc.so $(HOST_HDRS)
 	@mkdir -p tests/bin
-	g++ -O3 -g -std=c++17 -fPIC -shared -Wall -Wno-unused-result -Itests/mockhip -x c++ netc_amd/csrc/ws_ingest.hip netc_amd/csrc/ws_hub.hip netc_amd/csrc/ws_egress_hub.hip \
+	g++ $(MOCK_OPT) -g -std=c++17 -fPIC -shared -Wall -Wno-unused-result -Itests/mockhip -x c++ $(MOCK_SRCS) \
 	    -x none tests/mockhip/mock_gpu.cc -L$(LIBDIR) -lnetc -Wl,-Bsymbolic -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)' -o $@
 tests/bin/%_cpu: tests/drivers/%.c tests/bin/libnetc_hub_cpu.so $(LIBDIR)/libnetc.so $(HOST_HDRS)
 	$(CC) -O2 -g -Wall -std=gnu11 -Iinclude -o $@ $< -Ltests/bin -lnetc_hub_cpu -L$(LIBDIR) -lnetc \
 	    -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)' -lpthread -ldl
+
+# TEST ONLY: host/ws_header.h's decode and strict predicate as a library (tests/test_ring_shared.py)
+tests/bin/libws_header_shim.so: tests/drivers/ws_header_shim.c netc_amd/csrc/host/ws_header.h
+	@mkdir -p tests/bin
+	$(CC) $(CFLAGS) -shared -o $@ $<
 
 # the per-call cost of an attached socket's route lookups, close-tracked or fstat-checked (host only)
 tests/bin/ws_route_lookup: tests/drivers/ws_route_lookup.c $(LIBDIR)/libnetc.so $(HOST_HDRS)
@@ -133,7 +112,7 @@ clean:
 	rm -f $(LIBDIR)/*.so build/*.o tests/bin/ws_gpu_epoll tests/bin/ws_egress_bench tests/bin/ws_route_bench \
 	    tests/bin/libnetc_ingest_mock.so tests/bin/ws_hub_server tests/bin/ws_egress_hub_server tests/bin/ws_echo_server \
 	    tests/bin/ws_close_track tests/bin/ws_close_track_mock tests/bin/libnetc_hub_cpu.so tests/bin/*_cpu \
-	    tests/bin/ws_route_lookup
+	    tests/bin/ws_route_lookup tests/bin/libws_header_shim.so
 	$(MAKE) -C oracle clean
 
 # diagnostics (tools/, not part of the product)

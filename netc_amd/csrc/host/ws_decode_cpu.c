@@ -13,6 +13,7 @@
 
 #include "../../../include/ws/frame.h"
 #include "../../../include/ws/mask.h"
+#include "ws_header.h"
 
 int netc_ws_decode_frames_host(void *payload, size_t payload_capacity, uint64_t *offsets, uint64_t *msg_first,
                                uint8_t *msg_opcode, uint64_t *dresult, const void *wire, size_t len,
@@ -37,18 +38,13 @@ int netc_ws_decode_frames_host(void *payload, size_t payload_capacity, uint64_t 
     if (msg_first) msg_first[0] = 0;
     for (uint64_t k = 0; k < n; ++k) {
         const uint64_t p = hdr[k];
-        const unsigned second = w[p + 1], code = second & 0x7Fu;
-        const uint64_t ext = code == 126 ? 2 : code == 127 ? 8 : 0;
-        const uint64_t hl = 2 + ext + ((second & 0x80u) ? 4 : 0);
+        const uint64_t hl = ws_header_len_of(w[p + 1]);
         uint64_t plen;
         if (k + 1 < n || found <= max_frames) {
             plen = hdr[k + 1] - p - hl;
         } else {   /* max_frames cut the record short: hdr[n] is not there, the length is in the header */
-            plen = code;
-            if (ext) {
-                plen = 0;
-                for (uint64_t i = 0; i < ext; ++i) plen = (plen << 8) | w[p + 2 + i];
-            }
+            struct ws_header_view h;
+            plen = ws_header_decode(w + p, hl, &h) ? h.plen : 0;   /* (a recorded frame's header is whole) */
         }
         if (plen) {
             const uint32_t key = keys[k];

@@ -14,52 +14,7 @@
 
 #include "../../../include/ws/frame.h"
 #include "../../../include/ws/mask.h"
-
-/* one decoded header (decode() returns 0 when byte 1 or the extended length is not in the stream yet) */
-struct hdr_view
-{
-    uint64_t hlen;   /* header bytes: 2 + extended length + key */
-    uint64_t plen;   /* payload bytes */
-    uint32_t key;    /* packed key32 (0 if MASK is clear) */
-    uint8_t first, second;
-};
-
-static int decode(const uint8_t *w, uint64_t avail, struct hdr_view *h)
-{
-    if (avail < 2) return 0;
-    h->first = w[0];
-    h->second = w[1];
-    const unsigned code = h->second & 0x7Fu;
-    const uint64_t ext = code == 126 ? 2 : code == 127 ? 8 : 0;
-    const uint64_t key_bytes = (h->second & 0x80u) ? 4 : 0;
-    if (avail < 2 + ext) return 0;
-    uint64_t plen = code;
-    if (ext) {
-        plen = 0;
-        for (uint64_t i = 0; i < ext; ++i) plen = (plen << 8) | w[2 + i];
-    }
-    h->hlen = 2 + ext + key_bytes;
-    h->plen = plen;
-    h->key = 0;
-    if (key_bytes && avail >= h->hlen) {
-        uint32_t k;
-        memcpy(&k, w + 2 + ext, 4);   /* wire order k0 k1 k2 k3 -> little-endian key32 */
-        h->key = k;
-    }
-    return 1;
-}
-
-/* RFC 6455 §5.1, §5.2, §5.5: what a server must not accept from a client */
-static int forbidden(const struct hdr_view *h)
-{
-    const unsigned op = h->first & 0x0Fu;
-    if (!(h->second & 0x80u)) return 1;               /* MASK clear */
-    if (h->first & 0x70u) return 1;                   /* RSV1-3 */
-    if ((op >= 3 && op <= 7) || op >= 11) return 1;   /* reserved opcodes */
-    if (op >= 8 && (!(h->first & 0x80u) || h->plen > 125)) return 1;   /* control: FIN, <= 125 */
-    if ((h->second & 0x7Fu) == 127 && (h->plen >> 63)) return 1;     /* 64-bit length, top bit */
-    return 0;
-}
+#include "ws_header.h"
 
 int netc_ws_scan_frames_host(const void *wire, size_t len, uint64_t start, int flags, uint64_t *hdr,
                              uint32_t *keys, uint8_t *b0, size_t max_frames, uint64_t *result)
@@ -70,9 +25,10 @@ int netc_ws_scan_frames_host(const void *wire, size_t len, uint64_t start, int f
     const int strict = (flags & NETC_WS_SCAN_STRICT) != 0;
     uint64_t n = 0, p = start;
     uint64_t error = UINT64_MAX;
-    struct hdr_view h;
-    while (p < len && decode(w + p, len - p, &h)) {
-        if (strict && forbidden(&h)) {
+    struct ws_header_view h;
+    /* judged as soon as byte 1 and the extended length are there: the key may still be missing */
+    while (p < len && ws_header_decode(w + p, len - p, &h)) {
+        if (strict && ws_header_forbidden(&h)) {
             error = p;
             break;
         }

@@ -17,15 +17,16 @@
 //            include/ws/route.h), which goes out ahead of its later bytes; then the slot is
 //            free.  Slots go out in the order they were filled, so a connection's bytes keep its
 //            queue order, and a peer that stops reading holds up nobody but itself.
+//
+// The slot's buffers, frame split and submission are ws_ring_host.h's SendSlot, shared with the
+// single-connection ring (ws_egress.hip); the spans, generations, statistics and the deferred
+// list are the hub's own.
 #include <hip/hip_runtime.h>
 
 #include <errno.h>
 #include <limits.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include <string.h>
-#include <sys/socket.h>
-#include <sys/stat.h>
 #include <sys/uio.h>
 
 #include <deque>
@@ -33,16 +34,12 @@
 #include <unordered_map>
 #include <vector>
 
-#include "ws_mask_gpu.h"
+#include "ws_ring_host.h"
 
 extern "C" {
-#include "../../include/ws/mask.h"
-#include "../../include/ws/frame.h"
 #include "../../include/ws/egress.h"
 #include "../../include/ws/egress_hub.h"
-#include "../../include/ws/common.h"
 #include "../../include/ws/route.h"
-extern __thread int netc_errno_reason;   // include/utils/error.h
 }
 
 using netc_gpu::api_fail;
@@ -56,8 +53,8 @@ enum SlotState : int { kFree = 0, kFilling, kInflight };
 
 struct EhConn {
     int fd = -1;
-    uint64_t dev = 0, ino = 0;
-    int failed = 0;             // send() failed: its bytes are dropped, its calls return -1
+    SockId id;
+    int failed = 0;            // send() failed: its bytes are dropped, its calls return -1
     bool deferred = false;      // its send backlog holds bytes (on the hub's deferred list)
     uint64_t last_gen = 0;      // the slot filling this connection last queued into
     uint64_t queued = 0;        // its messages in slots not yet sent
@@ -69,59 +66,18 @@ struct Span {   // one message's wire bytes in its slot
     uint64_t w0, w1;
 };
 
-struct EhSlot {
-    uint8_t* h_pay = nullptr;    // pinned: queued payload bytes (slot_bytes)
-    uint8_t* h_tab = nullptr;    // offsets [0, 8 (mf + 1)), keys and header bytes in their regions
-    uint8_t* h_pack = nullptr;   // pinned: the table packed at submit (a failed submission leaves h_tab)
-    uint8_t* h_wire = nullptr;   // pinned: the slot's wire bytes (D2H target)
-    uint64_t* h_len = nullptr;   // pinned: the device's wire length (wo[n])
-    uint8_t* d_pay = nullptr;
-    uint8_t* d_tab = nullptr;
-    uint8_t* d_wire = nullptr;
-    uint64_t* d_wo = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
-    int state = kFree;
-    int masked = -1;             // the slot's frames are masked (1) or not (0); -1 while empty
-    int ext = -2;                // one length class (0, 2, 8), mixed (-1), none yet (-2)
-    uint64_t fill = 0, frames = 0, wire = 0, gen = 0;
+struct EhSlot : SendSlot {   // the shared send-side slot (ws_ring_host.h)
+    uint64_t gen = 0;
     uint32_t nconn = 0;
     std::vector<Span> spans;
 };
-
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int device) {
-        err = hipGetDevice(&prev);
-        if (err != hipSuccess || prev == device) return;
-        err = hipSetDevice(device);
-        switched = err == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (switched) (void)hipSetDevice(prev);
-    }
-};
-
-inline uint64_t header_len(uint64_t payload, bool masked) {   // src/ws/common.c:55-82
-    return 2 + (payload <= 125 ? 0 : (payload <= 0xFFFF ? 2 : 8)) + (masked ? 4 : 0);
-}
-
-bool sock_identity(int fd, uint64_t* dev, uint64_t* ino) {
-    struct stat st;
-    if (fstat(fd, &st) != 0 || !S_ISSOCK(st.st_mode)) return false;
-    *dev = (uint64_t)st.st_dev;
-    *ino = (uint64_t)st.st_ino;
-    return true;
-}
 
 }  // namespace
 
 struct netc_ws_egress_hub {
     int device = 0;
     int nslots = 0;
-    uint64_t slot_bytes = 0, max_frames = 0, wire_cap = 0, keys_at = 0, b0_at = 0;
+    SendLayout lay;
     EhSlot* slots = nullptr;
     int cur = -1;                // the filling slot
     std::deque<int> fifo;        // submitted slots, oldest first
@@ -133,45 +89,6 @@ struct netc_ws_egress_hub {
 
 namespace {
 
-void free_slot(int device, EhSlot& s) {
-    if (s.stream) {
-        (void)hipStreamSynchronize(s.stream);
-        (void)netc_gpu::release_enc_scratch(device, s.stream);
-    }
-    if (s.h_pay) (void)hipHostFree(s.h_pay);
-    if (s.h_tab) (void)hipHostFree(s.h_tab);
-    if (s.h_pack) (void)hipHostFree(s.h_pack);
-    if (s.h_wire) (void)hipHostFree(s.h_wire);
-    if (s.h_len) (void)hipHostFree(s.h_len);
-    if (s.d_pay) (void)hipFree(s.d_pay);
-    if (s.d_tab) (void)hipFree(s.d_tab);
-    if (s.d_wire) (void)hipFree(s.d_wire);
-    if (s.d_wo) (void)hipFree(s.d_wo);
-    if (s.done) (void)hipEventDestroy(s.done);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
-    s = EhSlot();
-}
-
-int alloc_slot(const netc_ws_egress_hub* h, EhSlot& s) {
-    hipError_t e;
-    const uint64_t tab = h->b0_at + h->max_frames;
-    if ((e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming)) != hipSuccess)
-        return api_fail_hip(NETC_GPU_ERUNTIME, "egress hub: stream / event create", e);
-    if ((e = hipHostMalloc((void**)&s.h_pay, h->slot_bytes, hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc((void**)&s.h_tab, tab, hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc((void**)&s.h_pack, tab, hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc((void**)&s.h_wire, h->wire_cap, hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc((void**)&s.h_len, sizeof(uint64_t), hipHostMallocDefault)) != hipSuccess)
-        return api_fail_hip(NETC_GPU_ENOMEM, "egress hub: pinned host allocation", e);
-    if ((e = hipMalloc((void**)&s.d_pay, h->slot_bytes)) != hipSuccess ||
-        (e = hipMalloc((void**)&s.d_tab, tab)) != hipSuccess ||
-        (e = hipMalloc((void**)&s.d_wire, h->wire_cap)) != hipSuccess ||
-        (e = hipMalloc((void**)&s.d_wo, (h->max_frames + 1) * sizeof(uint64_t))) != hipSuccess)
-        return api_fail_hip(NETC_GPU_ENOMEM, "egress hub: device allocation", e);
-    return 0;
-}
-
 // the filling slot goes to the GPU (see the file comment)
 int submit(netc_ws_egress_hub* h) {
     if (h->cur < 0) return 0;
@@ -181,39 +98,13 @@ int submit(netc_ws_egress_hub* h) {
         return api_fail(NETC_GPU_ELAUNCH, "egress hub: injected fault (NETC_GPU_KNOB_INJECT_FAULT)");
     DeviceGuard dg(h->device);
     if (dg.err != hipSuccess) return api_fail_hip(NETC_GPU_ERUNTIME, "hipSetDevice", dg.err);
-    const uint64_t n = s.frames;
-    uint64_t* off = (uint64_t*)s.h_pack;
-    uint8_t* keys = s.h_pack + (n + 1) * sizeof(uint64_t);
-    uint8_t* b0 = keys + n * sizeof(uint32_t);
-    const bool masked = s.masked == 1;
-    memcpy(off, s.h_tab, n * sizeof(uint64_t));
-    if (masked) memcpy(keys, s.h_tab + h->keys_at, n * sizeof(uint32_t));
-    memcpy(b0, s.h_tab + h->b0_at, n);
-    off[n] = s.fill;
-    const uint64_t tab = (uint64_t)(b0 + n - s.h_pack);
-    const uint64_t bound = s.fill + n * NETC_WS_MAX_HEADER(masked);
-    hipError_t e;
-    if ((s.fill && (e = hipMemcpyAsync(s.d_pay, s.h_pay, s.fill, hipMemcpyHostToDevice, s.stream)) != hipSuccess) ||
-        (e = hipMemcpyAsync(s.d_tab, s.h_pack, tab, hipMemcpyHostToDevice, s.stream)) != hipSuccess)
-        return api_fail_hip(NETC_GPU_ERUNTIME, "egress hub: H2D copy", e);
-    const uint8_t* d_keys = s.d_tab + (n + 1) * sizeof(uint64_t);
-    if ((e = netc_gpu::launch_encode_frames(s.d_wire, bound, s.d_pay, s.fill, (const uint64_t*)s.d_tab,
-                                            (const uint32_t*)d_keys, d_keys + n * sizeof(uint32_t), n, masked,
-                                            s.d_wo, s.stream, netc_gpu::api_cfg(), s.ext >= 0 ? s.ext : -1)) !=
-        hipSuccess)
-        return api_fail_hip(e == hipErrorOutOfMemory ? NETC_GPU_ENOMEM : NETC_GPU_ELAUNCH, "egress hub: frame assembly",
-                            e);
-    *s.h_len = ~0ull;
-    if ((e = hipMemcpyAsync(s.h_wire, s.d_wire, s.wire, hipMemcpyDeviceToHost, s.stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(s.h_len, s.d_wo + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream)) != hipSuccess ||
-        (e = hipEventRecord(s.done, s.stream)) != hipSuccess)
-        return api_fail_hip(NETC_GPU_ERUNTIME, "egress hub: D2H copy", e);
+    if (int r = send_slot_submit(h->lay, s, "egress hub")) return r;
     s.state = kInflight;
     h->fifo.push_back(h->cur);
     h->cur = -1;
     h->st.launches++;
     h->st.messages += s.spans.size();
-    h->st.frames += n;
+    h->st.frames += s.frames;
     h->st.wire_bytes += s.wire;
     h->st.connection_slots += s.nconn;
     if (s.nconn > h->st.max_connections) h->st.max_connections = s.nconn;
@@ -294,8 +185,7 @@ long send_oldest(netc_ws_egress_hub* h, bool* dropped) {
         // a connection closed without a detach that close tracking did not see (a raw close, a
         // process where close() does not reach libnetc.so): its descriptor may name another
         // connection by now, which must not get these bytes.  One fstat per connection per slot.
-        uint64_t d = 0, ino = 0;
-        if (!c->failed && !(sock_identity(c->fd, &d, &ino) && d == c->dev && ino == c->ino)) {
+        if (!c->failed && !same_socket(c->fd, c->id)) {
             c->failed = EBADF;
             h->st.send_errors++;
         }
@@ -347,54 +237,34 @@ int queue(netc_ws_egress_hub* h, EhConn* c, const void* payload, size_t len, uin
     if (len && !payload) return api_fail(NETC_GPU_EINVAL, "egress hub: null payload");
     const uint64_t nf = num_frames ? num_frames : 1;
     const int masked = masking_key ? 1 : 0;
-    if (len > h->slot_bytes || nf > h->max_frames)
+    const SendLayout& l = h->lay;
+    if (len > l.slot_bytes || nf > l.max_frames)
         return api_fail(NETC_WS_EGRESS_TOO_BIG, "egress hub: a message of %zu bytes in %llu frames exceeds a slot "
                         "(%llu bytes, %llu frames)", len, (unsigned long long)nf,
-                        (unsigned long long)h->slot_bytes, (unsigned long long)h->max_frames);
+                        (unsigned long long)l.slot_bytes, (unsigned long long)l.max_frames);
     if (int r = acquire(h)) return r;
     {
         const EhSlot& s = h->slots[h->cur];
         // a slot past its full mark is one whose submission failed: tried again (and reported)
         // before anything more is queued; a message that does not fit starts the next slot
-        const bool full = s.fill + 4096 > h->slot_bytes || s.frames + 64 > h->max_frames;
-        if (s.frames && (full || s.masked != masked || s.fill + len > h->slot_bytes || s.frames + nf > h->max_frames)) {
+        const bool full = s.fill + 4096 > l.slot_bytes || s.frames + 64 > l.max_frames;
+        if (s.frames && (full || s.masked != masked || s.fill + len > l.slot_bytes || s.frames + nf > l.max_frames)) {
             if (int e = submit(h)) return e;
             if (int r = acquire(h)) return r;
         }
     }
     EhSlot& s = h->slots[h->cur];
-    s.masked = masked;
-    if (len) memcpy(s.h_pay + s.fill, payload, len);
-    const uint64_t split = len / nf, rem = len % nf;   // the reference's split (src/ws/common.c:42-49)
-    uint64_t* off = (uint64_t*)s.h_tab + s.frames;
-    uint32_t* keys = (uint32_t*)(s.h_tab + h->keys_at) + s.frames;
-    uint8_t* b0 = s.h_tab + h->b0_at + s.frames;
-    const uint32_t key32 = masked ? (uint32_t)masking_key[0] | (uint32_t)masking_key[1] << 8 |
-                                        (uint32_t)masking_key[2] << 16 | (uint32_t)masking_key[3] << 24
-                                  : 0u;
-    uint64_t wire = 0;
-    for (uint64_t i = 0; i < nf; ++i) {
-        const bool last = i + 1 == nf;
-        const uint64_t flen = split + (last ? rem : 0);
-        off[i] = s.fill + i * split;
-        if (masked) keys[i] = key32;
-        b0[i] = (uint8_t)((last ? 0x80 : 0x00) | (i == 0 ? (opcode & 0x0F) : WS_OPCODE_CONTINUE));   // :55-61
-        wire += header_len(flen, masked) + flen;
-        const int ext = flen <= 125 ? 0 : (flen <= 0xFFFF ? 2 : 8);
-        s.ext = s.ext == -2 || s.ext == ext ? ext : -1;
-    }
-    s.spans.push_back(Span{c, s.wire, s.wire + wire});
+    const uint64_t w0 = s.wire;   // where its frames will sit in the slot's wire
+    const uint64_t wire = send_slot_append(s, l, payload, len, opcode, masking_key, nf);
+    s.spans.push_back(Span{c, w0, w0 + wire});
     ++c->queued;
     if (c->last_gen != s.gen) {
         c->last_gen = s.gen;
         ++s.nconn;
     }
-    s.fill += len;
-    s.frames += nf;
-    s.wire += wire;
     // full: on its way now.  The message is queued either way; a failed submission leaves the slot
     // filling, and the next queue or flush tries it again and reports it (before queueing anything).
-    if (s.fill + 4096 > h->slot_bytes || s.frames + 64 > h->max_frames) (void)submit(h);
+    if (s.fill + 4096 > l.slot_bytes || s.frames + 64 > l.max_frames) (void)submit(h);
     return 0;
 }
 
@@ -483,19 +353,15 @@ int netc_ws_egress_hub_create(struct netc_ws_egress_hub** out, int device, size_
     if (!h) return api_fail(NETC_GPU_ENOMEM, "egress hub: host allocation");
     h->device = device;
     h->nslots = nslots;
-    h->slot_bytes = slot_bytes;
-    h->max_frames = max_frames;
-    h->wire_cap = slot_bytes + max_frames * NETC_WS_MAX_HEADER(1);
-    h->keys_at = (max_frames + 1) * sizeof(uint64_t);
-    h->b0_at = h->keys_at + max_frames * sizeof(uint32_t);
+    h->lay = send_layout(slot_bytes, max_frames);
     h->slots = new (std::nothrow) EhSlot[nslots];
     if (!h->slots) {
         delete h;
         return api_fail(NETC_GPU_ENOMEM, "egress hub: host allocation");
     }
     for (int i = 0; i < nslots; ++i) {
-        if (int r = alloc_slot(h, h->slots[i])) {
-            for (int j = 0; j <= i; ++j) free_slot(device, h->slots[j]);
+        if (int r = send_slot_alloc(h->lay, h->slots[i], "egress hub")) {
+            for (int j = 0; j <= i; ++j) send_slot_free(device, h->slots[j]);
             delete[] h->slots;
             delete h;
             return r;
@@ -516,20 +382,20 @@ void netc_ws_egress_hub_destroy(struct netc_ws_egress_hub* h) {
         delete kv.second;
     }
     h->conns.clear();
-    for (int i = 0; i < h->nslots; ++i) free_slot(h->device, h->slots[i]);
+    for (int i = 0; i < h->nslots; ++i) send_slot_free(h->device, h->slots[i]);
     delete[] h->slots;
     delete h;
 }
 
 int netc_ws_gpu_attach_send_hub(int sockfd, struct netc_ws_egress_hub* h) {
     if (!h) return api_fail(NETC_GPU_EINVAL, "attach_send_hub: null hub");
-    uint64_t dev = 0, ino = 0;
-    if (!sock_identity(sockfd, &dev, &ino))
+    SockId id;
+    if (!sock_identity(sockfd, &id))
         return api_fail(NETC_GPU_EINVAL, "attach_send_hub: %d is not an open socket", sockfd);
     auto it = h->conns.find(sockfd);
     if (it != h->conns.end()) {
-        if (it->second->dev == dev && it->second->ino == ino) return 0;   // already this connection
-        forget(h, it->second);                                             // closed without a detach
+        if (it->second->id == id) return 0;   // already this connection
+        forget(h, it->second);                // closed without a detach
         h->conns.erase(it);
         void* ctx = nullptr;
         if (netc_ws_send_route_get_raw(sockfd, &ctx) == hub_send_route && ctx == h) (void)netc_ws_send_route_detach(sockfd);
@@ -537,8 +403,7 @@ int netc_ws_gpu_attach_send_hub(int sockfd, struct netc_ws_egress_hub* h) {
     EhConn* c = new (std::nothrow) EhConn();
     if (!c) return api_fail(NETC_GPU_ENOMEM, "attach_send_hub: host allocation");
     c->fd = sockfd;
-    c->dev = dev;
-    c->ino = ino;
+    c->id = id;
     if (netc_ws_send_route_attach(sockfd, hub_send_route, h) != 0) {
         delete c;
         return api_fail(NETC_GPU_EINVAL, "attach_send_hub: socket %d: %s", sockfd,
@@ -560,8 +425,7 @@ int netc_ws_gpu_detach_send_hub(int sockfd) {
         if (it != h->conns.end()) {
             DeviceGuard dg(h->device);
             // ws_send_message already returned 1 for what it queued: it goes out first
-            uint64_t d = 0, i = 0;
-            if (!(sock_identity(sockfd, &d, &i) && d == it->second->dev && i == it->second->ino))
+            if (!same_socket(sockfd, it->second->id))
                 it->second->failed = EBADF;   // closed without a detach: its bytes have nowhere to go
             if (it->second->queued || it->second->deferred) flushed = flush(h);
             forget(h, it->second);

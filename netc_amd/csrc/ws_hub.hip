@@ -17,31 +17,27 @@
 //            reference's rules (src/ws/common.c:163-164, 210-216, 303-309, 333-347).
 //
 // A slot is free again when every connection has consumed its ranges in it.
+//
+// The peeked socket (peek, consume, the hostage byte's accounting) and the message reassembly
+// are ws_ring_host.h's PeekSock and MsgBuf, shared with the ingest ring (ws_ingest.hip); headers
+// are read with host/ws_header.h, as libnetc's host walk reads them.
 #include <hip/hip_runtime.h>
 
 #include <errno.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/ioctl.h>
 #include <sys/socket.h>
-#include <sys/stat.h>
-#include <sys/uio.h>
 
 #include <deque>
 #include <new>
 #include <unordered_map>
 
-#include "ws_mask_gpu.h"
+#include "ws_ring_host.h"
 
 extern "C" {
-#include "../../include/ws/mask.h"
-#include "../../include/ws/frame.h"
-#include "../../include/ws/ingest.h"
 #include "../../include/ws/hub.h"
-#include "../../include/ws/common.h"
 #include "../../include/ws/route.h"
-extern __thread int netc_errno_reason;   // include/utils/error.h
 }
 
 using netc_gpu::api_fail;
@@ -49,9 +45,7 @@ using netc_gpu::api_fail_hip;
 
 namespace {
 
-constexpr int kBadRecv = 10;                 // netc's BADRECV reason (include/utils/error.h)
 constexpr size_t kPeek = 256u << 10;         // bytes one take reads at most
-constexpr size_t kScratch = 1u << 20;        // discard buffer of non-TCP sockets
 
 enum SlotState : int { kFree = 0, kFilling, kInflight, kDone };
 
@@ -78,15 +72,11 @@ struct Range {
 };
 
 struct HubConn {
-    int fd = -1;
-    uint64_t dev = 0, ino = 0;
-    int tcp = 0;
-    uint64_t in_pos = 0, sock_pos = 0;   // stream bytes peeked / removed from the socket
+    PeekSock sock;                       // its socket, and the stream bytes removed from it (ws_ring_host.h)
+    uint64_t in_pos = 0;                 // stream bytes peeked
     uint8_t* carry = nullptr;            // the incomplete frame's bytes
     size_t carry_len = 0, carry_cap = 0;
-    uint8_t* mbuf = nullptr;             // the message so far
-    size_t msize = 0, mcap = 0;
-    uint8_t opcode = 0;
+    MsgBuf msg;                          // the message so far
     std::deque<Range> ranges;
     uint64_t last_gen = 0;               // the slot filling this connection last added frames to
     int err = 0;                         // sticky (delivered)
@@ -94,22 +84,6 @@ struct HubConn {
     bool carry_frames = false;           // the carry may hold complete frames (a full frame table
                                          // stopped the walk): walked before new bytes, hostage kept
     bool closed = false;
-    uint8_t* scratch = nullptr;
-};
-
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int device) {
-        err = hipGetDevice(&prev);
-        if (err != hipSuccess || prev == device) return;
-        err = hipSetDevice(device);
-        switched = err == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (switched) (void)hipSetDevice(prev);
-    }
 };
 
 }  // namespace
@@ -165,7 +139,6 @@ void maybe_free(HubSlot& s) {
 }
 
 void drop_conn(netc_ws_hub* h, HubConn* c);
-bool sock_identity(int fd, uint64_t* dev, uint64_t* ino);
 int hub_route(void* ctx, int sockfd, struct ws_frame_parsing_state* state, size_t max_payload_length);
 
 // Connections closed without a detach that close tracking did not see (include/ws/route.h): their
@@ -173,11 +146,11 @@ int hub_route(void* ctx, int sockfd, struct ws_frame_parsing_state* state, size_
 size_t sweep_closed(netc_ws_hub* h) {
     size_t n = 0;
     for (auto it = h->conns.begin(); it != h->conns.end();) {
-        uint64_t d = 0, i = 0;
         HubConn* c = it->second;
-        if (!c->ranges.empty() && !(sock_identity(c->fd, &d, &i) && d == c->dev && i == c->ino)) {
+        const int fd = c->sock.fd;
+        if (!c->ranges.empty() && !same_socket(fd, c->sock.id)) {
             void* ctx = nullptr;
-            if (netc_ws_route_get_raw(c->fd, &ctx) == hub_route && ctx == h) (void)netc_ws_route_detach(c->fd);
+            if (netc_ws_route_get_raw(fd, &ctx) == hub_route && ctx == h) (void)netc_ws_route_detach(fd);
             drop_conn(h, c);
             it = h->conns.erase(it);
             ++n;
@@ -253,37 +226,6 @@ int submit(netc_ws_hub* h) {
     return 0;
 }
 
-// header decode (src/ws/common.c:146-296): header length, payload length; false if the bytes
-// there do not hold the whole header yet
-bool decode(const uint8_t* p, size_t room, uint64_t* hl, uint64_t* pl) {
-    if (room < 2) return false;
-    const uint8_t second = p[1];
-    const uint64_t code = second & 0x7F;
-    const uint64_t ext = code == 126 ? 2 : code == 127 ? 8 : 0;
-    const uint64_t h = 2 + ext + ((second & 0x80) ? 4 : 0);
-    if (room < h) return false;
-    uint64_t len = code;
-    if (ext) {
-        len = 0;
-        for (uint64_t i = 0; i < ext; ++i) len = len << 8 | p[2 + i];
-    }
-    *hl = h;
-    *pl = len;
-    return true;
-}
-
-// the checks of NETC_WS_INGEST_STRICT (RFC 6455 §5.1-5.5; as ws_scan_cpu.c)
-bool forbidden(const uint8_t* p, uint64_t pl) {
-    const uint8_t first = p[0], second = p[1];
-    const unsigned op = first & 0x0F;
-    if (!(second & 0x80)) return true;
-    if (first & 0x70) return true;
-    if ((op >= 3 && op <= 7) || op >= 11) return true;
-    if (op >= 8 && (!(first & 0x80) || pl > 125)) return true;
-    if ((second & 0x7F) == 127 && (pl >> 63)) return true;
-    return false;
-}
-
 // Complete frames of [buf, buf + len), recorded from table entry `at` on (at most cap of them):
 // *cut = where the first frame not recorded starts; *err = the code that stops the stream
 // there (PAYLOAD_TOO_BIG / INVALID_FRAME_LENGTH), 0 if it is only incomplete or the table full.
@@ -293,69 +235,32 @@ uint64_t walk(const netc_ws_hub* h, HubSlot& s, const uint8_t* buf, uint64_t bas
     *err = 0;
     uint32_t* keys = (uint32_t*)(s.hdr() + h->max_frames + 1);
     while (n < cap) {
-        uint64_t hl = 0, pl = 0;
-        if (!decode(buf + p, len - p, &hl, &pl)) break;
-        if (h->strict && forbidden(buf + p, pl)) {
+        // a frame is judged (strict, then the frame limit) only once its whole header, key
+        // included, is there (host/ws_header.h; the host walk of ws_scan_cpu.c judges earlier)
+        struct ws_header_view f;
+        if (!ws_header_decode(buf + p, len - p, &f) || len - p < f.hlen) break;
+        if (h->strict && ws_header_forbidden(&f)) {
             *err = WS_FRAME_PARSE_ERROR_INVALID_FRAME_LENGTH;
             break;
         }
-        if (pl > h->max_frame) {
+        if (f.plen > h->max_frame) {
             *err = WS_FRAME_PARSE_ERROR_PAYLOAD_TOO_BIG;
             break;
         }
-        if (hl + pl > len - p) break;   // not complete yet
+        if (f.hlen + f.plen > len - p) break;   // not complete yet
         const uint64_t k = s.nframes + n;
         s.hdr()[k] = base + p;
-        uint32_t key = 0;
-        if (buf[p + 1] & 0x80) memcpy(&key, buf + p + hl - 4, 4);
-        keys[k] = key;
-        s.b0[k] = buf[p];
+        keys[k] = f.key;
+        s.b0[k] = f.first;
         ++n;
-        p += hl + pl;
+        p += f.hlen + f.plen;
     }
     *cut = p;
     return n;
 }
 
 // remove the socket's bytes up to stream position `to` (<= in_pos; the hub has them)
-int sock_consume(HubConn& c, uint64_t to) {
-    while (c.sock_pos < to) {
-        const uint64_t want = to - c.sock_pos;
-        ssize_t r;
-        if (c.tcp) {
-            r = recv(c.fd, nullptr, (size_t)want, MSG_TRUNC | MSG_DONTWAIT);
-            if (r < 0 && errno == EFAULT) {
-                c.tcp = 0;
-                continue;
-            }
-        } else {
-            if (!c.scratch && !(c.scratch = (uint8_t*)malloc(kScratch)))
-                return api_fail(NETC_GPU_ENOMEM, "hub: discard buffer");
-            r = recv(c.fd, c.scratch, (size_t)(want < kScratch ? want : kScratch), MSG_DONTWAIT);
-        }
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) {
-            const int saved = r < 0 ? errno : ECONNRESET;
-            api_fail(NETC_WS_INGEST_ERECV, "hub: removing read bytes from socket %d: %s", c.fd, strerror(saved));
-            netc_errno_reason = kBadRecv;
-            errno = saved;
-            return NETC_WS_INGEST_ERECV;
-        }
-        c.sock_pos += (uint64_t)r;
-    }
-    return 0;
-}
-
-bool grow(uint8_t*& buf, size_t& cap, size_t need) {
-    if (need <= cap && buf) return true;
-    size_t c = cap ? cap : 256;
-    while (c < need) c *= 2;
-    uint8_t* nb = (uint8_t*)realloc(buf, c);
-    if (!nb) return false;
-    buf = nb;
-    cap = c;
-    return true;
-}
+int conn_consume(HubConn& c, uint64_t to) { return sock_consume(c.sock, to, "hub", "read"); }
 
 // One take (see the file comment): new bytes (> 0; *frames = complete frames added to the
 // filling slot), 0 when the socket has nothing new, or a code (NETC_WS_INGEST_CLOSED / FULL / ...).
@@ -375,26 +280,20 @@ long take(netc_ws_hub* h, HubConn& c, uint64_t* frames) {
     if (c.carry_len) memcpy(dst, c.carry, c.carry_len);
     size_t room = (size_t)(h->slot_bytes - seg - c.carry_len);
     if (room > kPeek) room = kPeek;
-    const int held = (int)(c.in_pos - c.sock_pos);
-    if (held > 1) return api_fail(NETC_GPU_ERUNTIME, "hub: %d bytes held in socket %d", held, c.fd);
+    const int fd = c.sock.fd;
+    const int held = (int)(c.in_pos - c.sock.sock_pos);
+    if (held > 1) return api_fail(NETC_GPU_ERUNTIME, "hub: %d bytes held in socket %d", held, fd);
     // a carry with complete frames is walked even when the socket has nothing new, and the
     // hostage stays: the caller must come back for those frames' messages
     const bool stale = c.carry_frames;
     ssize_t r;
     bool eof = false;
     for (int pass = 0;; ++pass) {
-        uint8_t skip[1];
-        const int k = (int)(c.in_pos - c.sock_pos);
-        struct iovec iov[2] = {{skip, (size_t)k}, {dst + c.carry_len, room}};
-        struct msghdr mh;
-        memset(&mh, 0, sizeof mh);
-        mh.msg_iov = k ? iov : iov + 1;
-        mh.msg_iovlen = k ? 2 : 1;
-        do r = recvmsg(c.fd, &mh, MSG_PEEK | MSG_DONTWAIT);   // (never blocks the loop, blocking socket or not)
-        while (r < 0 && errno == EINTR);
+        const int k = (int)(c.in_pos - c.sock.sock_pos);
+        r = sock_peek(c.sock, k, dst + c.carry_len, room);   // (never blocks the loop, blocking socket or not)
         if (r > 0 && r <= k) {   // only the hostage: release it and look once more
             if (pass == 0 && held && !stale) {
-                if (int e = sock_consume(c, c.in_pos)) return e;
+                if (int e = conn_consume(c, c.in_pos)) return e;
                 continue;
             }
             r = 0;
@@ -405,17 +304,11 @@ long take(netc_ws_hub* h, HubConn& c, uint64_t* frames) {
         break;
     }
     if (r < 0) {
-        if (errno != EAGAIN && errno != EWOULDBLOCK) {
-            const int saved = errno;
-            api_fail(NETC_WS_INGEST_ERECV, "hub: recv on socket %d: %s", c.fd, strerror(saved));
-            netc_errno_reason = kBadRecv;
-            errno = saved;
-            return NETC_WS_INGEST_ERECV;
-        }
+        if (errno != EAGAIN && errno != EWOULDBLOCK) return recv_failed(errno, "hub: recv on socket %d", fd);
         r = 0;
     }
     if (r == 0 && !stale) {
-        if (eof) return api_fail(NETC_WS_INGEST_CLOSED, "hub: socket %d: the peer closed the connection", c.fd);
+        if (eof) return api_fail(NETC_WS_INGEST_CLOSED, "hub: socket %d: the peer closed the connection", fd);
         return 0;
     }
     c.in_pos += (uint64_t)r;
@@ -441,18 +334,11 @@ long take(netc_ws_hub* h, HubConn& c, uint64_t* frames) {
     if (tail && !grow(c.carry, c.carry_cap, tail)) return api_fail(NETC_GPU_ENOMEM, "hub: carry buffer");
     if (tail) memmove(c.carry, dst + cut, tail);
     c.carry_len = tail;
-    if (c.in_pos > c.sock_pos + 1)
-        if (int e = sock_consume(c, c.in_pos - 1)) return e;
+    if (c.in_pos > c.sock.sock_pos + 1)
+        if (int e = conn_consume(c, c.in_pos - 1)) return e;
     *frames = n;
     if (s.fill + 4096 > h->slot_bytes || c.carry_frames) (void)submit(h);   // full: on its way now (errors resurface)
     return r > 0 ? r : (n > 0 || c.carry_frames ? 1 : 0);   // > 0: progress (new bytes or carried frames)
-}
-
-bool m_append(HubConn& c, const uint8_t* p, size_t n) {
-    if (!grow(c.mbuf, c.mcap, c.msize + n)) return false;
-    if (n) memcpy(c.mbuf + c.msize, p, n);
-    c.msize += n;
-    return true;
 }
 
 // The connection's next message from its ranges: 0 (filled), 1 (no frames pending), 2 (its next
@@ -472,21 +358,12 @@ int deliver(netc_ws_hub* h, HubConn& c, struct ws_message* out, size_t max_paylo
         while (r.next < r.n) {
             const uint64_t k = r.k0 + r.next++;
             const uint8_t* f = s.h_buf + hdr[k];
-            uint64_t hl = 0, pl = 0;
-            (void)decode(f, hdr[k + 1] - hdr[k], &hl, &pl);
-            const uint8_t b0 = s.b0[k], op = b0 & 0x0F;
-            if (op != WS_OPCODE_CONTINUE) c.opcode = op;                       // :163-164
-            if (pl + c.msize > max_payload_length) return WS_FRAME_PARSE_ERROR_PAYLOAD_TOO_BIG;   // :210, :261
-            if (!m_append(c, f + hl, (size_t)pl)) return api_fail(NETC_GPU_ENOMEM, "hub: message buffer");
-            if (b0 & 0x80) {                                                   // FIN (:340-346)
-                if (c.opcode == WS_OPCODE_TEXT && !m_append(c, (const uint8_t*)"", 1))
-                    return api_fail(NETC_GPU_ENOMEM, "hub: message buffer");
-                if (!c.mbuf && !(c.mbuf = (uint8_t*)malloc(1))) return api_fail(NETC_GPU_ENOMEM, "hub: message buffer");
-                out->opcode = c.opcode;
-                out->buffer = c.mbuf;
-                out->payload_length = c.msize;
-                c.mbuf = nullptr;
-                c.msize = c.mcap = 0;
+            struct ws_header_view fh = {};
+            (void)ws_header_decode(f, hdr[k + 1] - hdr[k], &fh);
+            const int a = msg_add_frame(c.msg, s.b0[k], f + fh.hlen, fh.plen, max_payload_length, out);
+            if (a == NETC_GPU_ENOMEM) return api_fail(NETC_GPU_ENOMEM, "hub: message buffer");
+            if (a < 0) return a;
+            if (a == 0) {
                 if (r.next == r.n) {
                     --s.refs;
                     maybe_free(s);
@@ -502,6 +379,13 @@ int deliver(netc_ws_hub* h, HubConn& c, struct ws_message* out, size_t max_paylo
     return 1;
 }
 
+void free_conn(HubConn* c) {
+    free(c->carry);
+    free(c->msg.buf);
+    free(c->sock.scratch);
+    delete c;
+}
+
 void drop_conn(netc_ws_hub* h, HubConn* c) {
     for (const Range& r : c->ranges) {
         HubSlot& s = h->slots[r.slot];
@@ -511,18 +395,7 @@ void drop_conn(netc_ws_hub* h, HubConn* c) {
             maybe_free(s);
         }
     }
-    free(c->carry);
-    free(c->mbuf);
-    free(c->scratch);
-    delete c;
-}
-
-bool sock_identity(int fd, uint64_t* dev, uint64_t* ino) {
-    struct stat st;
-    if (fstat(fd, &st) != 0 || !S_ISSOCK(st.st_mode)) return false;
-    *dev = (uint64_t)st.st_dev;
-    *ino = (uint64_t)st.st_ino;
-    return true;
+    free_conn(c);
 }
 
 // close() on an attached socket (close tracking, include/ws/route.h): its frames stop holding slots
@@ -542,7 +415,7 @@ int hub_route(void* ctx, int sockfd, struct ws_frame_parsing_state* state, size_
         if (r == 0) {
             // nothing of it left -- no frames, no error still to report, no carried frames (its
             // bytes are in the socket as far as the caller is concerned): no hostage
-            if (c.ranges.empty() && !c.pending && !c.carry_frames) (void)sock_consume(c, c.in_pos);
+            if (c.ranges.empty() && !c.pending && !c.carry_frames) (void)conn_consume(c, c.in_pos);
             state->message = m;
             return 0;
         }
@@ -564,7 +437,7 @@ int hub_route(void* ctx, int sockfd, struct ws_frame_parsing_state* state, size_
             continue;
         }
         if (n == 0) {
-            if (c.ranges.empty() && !c.pending && !c.carry_frames) (void)sock_consume(c, c.in_pos);
+            if (c.ranges.empty() && !c.pending && !c.carry_frames) (void)conn_consume(c, c.in_pos);
             return 1;
         }
         if (n == NETC_WS_INGEST_CLOSED) {
@@ -627,10 +500,7 @@ void netc_ws_hub_destroy(struct netc_ws_hub* h) {
     for (auto& kv : h->conns) {
         void* ctx = nullptr;
         if (netc_ws_route_get_raw(kv.first, &ctx) == hub_route && ctx == h) (void)netc_ws_route_detach(kv.first);
-        free(kv.second->carry);
-        free(kv.second->mbuf);
-        free(kv.second->scratch);
-        delete kv.second;
+        free_conn(kv.second);
     }
     h->conns.clear();
     for (int i = 0; i < h->nslots; ++i) free_slot(h->slots[i]);
@@ -640,25 +510,21 @@ void netc_ws_hub_destroy(struct netc_ws_hub* h) {
 
 int netc_ws_gpu_attach_hub(int sockfd, struct netc_ws_hub* h) {
     if (!h) return api_fail(NETC_GPU_EINVAL, "attach_hub: null hub");
-    uint64_t dev = 0, ino = 0;
-    if (!sock_identity(sockfd, &dev, &ino)) return api_fail(NETC_GPU_EINVAL, "attach_hub: %d is not an open socket", sockfd);
+    SockId id;
+    if (!sock_identity(sockfd, &id)) return api_fail(NETC_GPU_EINVAL, "attach_hub: %d is not an open socket", sockfd);
     auto it = h->conns.find(sockfd);
     if (it != h->conns.end()) {
-        if (it->second->dev == dev && it->second->ino == ino) return 0;   // already this connection
-        drop_conn(h, it->second);                                          // closed without a detach
+        if (it->second->sock.id == id) return 0;   // already this connection
+        drop_conn(h, it->second);                  // closed without a detach
         h->conns.erase(it);
     }
-    int type = 0, domain = 0;
-    socklen_t tl = sizeof type, dl = sizeof domain;
-    if (getsockopt(sockfd, SOL_SOCKET, SO_TYPE, &type, &tl) != 0 || type != SOCK_STREAM)
-        return api_fail(NETC_GPU_EINVAL, "attach_hub: socket %d is not a stream socket", sockfd);
-    (void)getsockopt(sockfd, SOL_SOCKET, SO_DOMAIN, &domain, &dl);
+    const int kind = stream_socket_kind(sockfd);
+    if (kind == kNotStream) return api_fail(NETC_GPU_EINVAL, "attach_hub: socket %d is not a stream socket", sockfd);
     HubConn* c = new (std::nothrow) HubConn();
     if (!c) return api_fail(NETC_GPU_ENOMEM, "attach_hub: host allocation");
-    c->fd = sockfd;
-    c->dev = dev;
-    c->ino = ino;
-    c->tcp = domain == AF_INET || domain == AF_INET6;
+    c->sock.fd = sockfd;
+    c->sock.id = id;
+    c->sock.tcp = kind == kStreamTcp;
     if (netc_ws_route_attach(sockfd, hub_route, h) != 0) {
         delete c;
         return api_fail(NETC_GPU_EINVAL, "attach_hub: socket %d: %s", sockfd,

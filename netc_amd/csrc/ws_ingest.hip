@@ -24,6 +24,9 @@
 // frame as they are, so the copy back writes them unchanged.  They are copied in
 // front of the next slot's received bytes (each slot keeps max-frame headroom in
 // front for that), so every H2D is one contiguous range and every frame is whole.
+//
+// The route's socket (peek, consume) and the message reassembly are ws_ring_host.h's PeekSock
+// and MsgBuf, shared with the receive hub (ws_hub.hip).
 #include <hip/hip_runtime.h>
 
 #include <errno.h>
@@ -32,29 +35,19 @@
 #include <string.h>
 #include <sys/socket.h>
 #include <sys/ioctl.h>
-#include <sys/stat.h>
-#include <sys/uio.h>
 
 #include <new>
 
-#include "ws_mask_gpu.h"
+#include "ws_ring_host.h"
 
 extern "C" {
-#include "../../include/ws/mask.h"
-#include "../../include/ws/frame.h"
-#include "../../include/ws/ingest.h"
-#include "../../include/ws/common.h"
 #include "../../include/ws/route.h"
-extern __thread int netc_errno_reason;   // include/utils/error.h
 }
 
 using netc_gpu::api_fail;
 using netc_gpu::api_fail_hip;
 
 namespace {
-
-constexpr int kBadRecv = 10;   // netc's BADRECV reason (include/utils/error.h)
-constexpr size_t kScratch = 1u << 20;   // discard buffer of the route on non-TCP sockets
 
 // Default scan choice per slot: the host header walk when the previous slot's frames
 // averaged at least this many bytes.  The walk costs the submitting thread one header
@@ -94,43 +87,14 @@ struct IngestSlot {
     bool slow_scan = false;      // the GPU scan walked part of the slot serially (diag != 0, e.g. RSV headers)
 };
 
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int device) {
-        err = hipGetDevice(&prev);
-        if (err != hipSuccess || prev == device) return;
-        err = hipSetDevice(device);
-        switched = err == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (switched) (void)hipSetDevice(prev);
-    }
-};
-
-// the message-level reader (netc_ws_ingest_next_message): the reference's reassembly
-// state, src/ws/common.c:163-164,210-216,303-309,333-347
+// the message-level reader (netc_ws_ingest_next_message)
 struct MessageState {
     bool have = false;           // a batch is taken and being read
     netc_ws_batch batch{};
     uint64_t k = 0;              // next frame of the batch
-    uint8_t* buf = nullptr;      // the message so far (malloc; the caller's once delivered)
-    size_t size = 0, cap = 0;
-    uint8_t opcode = 0;          // the last non-continuation frame's opcode, as the reference
+    MsgBuf m;                    // the message so far (ws_ring_host.h)
     int err = 0;                 // sticky message-level error (WS_FRAME_PARSE_ERROR_*)
     uint64_t end_pos = 0;        // stream position just past the last delivered message
-};
-
-// the socket a ring serves through ws_parse_frame (netc_ws_gpu_attach), and how far the
-// route has taken bytes out of it: the route reads ahead with MSG_PEEK and removes bytes
-// from the socket only up to the end of the message it returns (see gpu_route)
-struct RouteState {
-    int fd = -1;                 // attached socket, -1 = none
-    uint64_t dev = 0, ino = 0;   // its identity at attach time (fstat), against fd reuse
-    int tcp = 0;                 // TCP: discard with MSG_TRUNC (no copy); else recv into scratch
-    uint64_t sock_pos = 0;       // stream bytes removed from the socket
-    uint8_t* scratch = nullptr;  // discard buffer for non-TCP sockets
 };
 
 }  // namespace
@@ -154,7 +118,10 @@ struct netc_ws_ingest {
     bool closed = false;   // recv saw the peer close
     uint64_t in_pos = 0;   // stream bytes taken into the ring (recv / peek / write)
     MessageState msg;
-    RouteState route;
+    // the socket the ring serves through ws_parse_frame (netc_ws_gpu_attach), and how far the
+    // route has taken bytes out of it: the route reads ahead with MSG_PEEK and removes bytes
+    // from the socket only up to the end of the message it returns (see gpu_route)
+    PeekSock route;
 };
 
 namespace {
@@ -424,7 +391,7 @@ int netc_ws_ingest_create(struct netc_ws_ingest** out, int device, size_t slot_b
 
 void netc_ws_ingest_destroy(struct netc_ws_ingest* g) {
     if (!g) return;
-    free(g->msg.buf);   // a message not completed yet (delivered ones are the caller's)
+    free(g->msg.m.buf);   // a message not completed yet (delivered ones are the caller's)
     free(g->route.scratch);
     DeviceGuard dg(g->device);
     for (int i = 0; i < g->nslots; ++i) free_slot(g->slots[i]);
@@ -456,27 +423,14 @@ static long ring_recv(netc_ws_ingest* g, int fd, int skip = -1) {
         do r = recv(fd, dst, room, 0);
         while (r < 0 && errno == EINTR);
     } else {
-        uint8_t held[1];
-        if (skip > (int)sizeof held) return api_fail(NETC_GPU_ERUNTIME, "ingest: %d bytes held in the socket", skip);
-        struct iovec iov[2] = {{held, (size_t)skip}, {dst, room}};
-        struct msghdr mh;
-        memset(&mh, 0, sizeof mh);
-        mh.msg_iov = skip ? iov : iov + 1;
-        mh.msg_iovlen = skip ? 2 : 1;
-        // MSG_DONTWAIT: the route peeks again after releasing its hostage, when the socket may
-        // hold nothing -- a blocking socket must not stall the caller's loop there
-        do r = recvmsg(fd, &mh, MSG_PEEK | MSG_DONTWAIT);
-        while (r < 0 && errno == EINTR);
+        if (skip > 1) return api_fail(NETC_GPU_ERUNTIME, "ingest: %d bytes held in the socket", skip);
+        r = sock_peek(g->route, skip, dst, room);   // (fd is the route's socket: gpu_route checked)
         if (r > 0 && r <= skip) return 0;   // only what the ring already has
         if (r > 0) r -= skip;
     }
     if (r < 0) {
         if (errno == EAGAIN || errno == EWOULDBLOCK) return 0;
-        const int saved = errno;
-        api_fail(NETC_WS_INGEST_ERECV, "ingest: recv: %s", strerror(saved));
-        netc_errno_reason = kBadRecv;
-        errno = saved;
-        return NETC_WS_INGEST_ERECV;
+        return recv_failed(errno, "ingest: recv");
     }
     if (r == 0) {   // the peer closed: what it sent goes to the GPU
         g->closed = true;
@@ -597,7 +551,7 @@ static int message_code(int r) {
 
 // a new message whose frames up to FIN are all in the batch: its buffer at its exact size
 // (the payloads + a NUL), so the appends never reallocate and copy it again
-static void msg_reserve_exact(MessageState& m, const netc_ws_batch& b, uint64_t k) {
+static void msg_reserve_exact(MsgBuf& m, const netc_ws_batch& b, uint64_t k) {
     uint64_t need = 1;
     for (uint64_t j = k, stop = k + 1024 < b.nframes ? k + 1024 : b.nframes; j < stop; ++j) {
         uint64_t off = 0, len = 0;
@@ -608,20 +562,6 @@ static void msg_reserve_exact(MessageState& m, const netc_ws_batch& b, uint64_t 
             return;
         }
     }
-}
-
-static bool msg_append(MessageState& m, const uint8_t* p, size_t n) {
-    if (m.size + n > m.cap || !m.buf) {
-        size_t cap = m.cap ? m.cap : 64;
-        while (cap < m.size + n) cap *= 2;
-        uint8_t* nb = (uint8_t*)realloc(m.buf, cap);
-        if (!nb) return false;
-        m.buf = nb;
-        m.cap = cap;
-    }
-    if (n) memcpy(m.buf + m.size, p, n);
-    m.size += n;
-    return true;
 }
 
 int netc_ws_ingest_next_message(struct netc_ws_ingest* g, struct ws_message* message, size_t max_payload_length,
@@ -649,27 +589,14 @@ int netc_ws_ingest_next_message(struct netc_ws_ingest* g, struct ws_message* mes
         const netc_ws_batch& b = m.batch;
         while (m.k < b.nframes) {
             const uint64_t k = m.k++;
-            const uint8_t b0 = b.b0[k];
-            const uint8_t op = b0 & 0x0F;
             uint64_t off = 0, len = 0;
             (void)netc_ws_batch_payload(&b, k, &off, &len);
-            if (op != WS_OPCODE_CONTINUE) m.opcode = op;                        // :163-164
-            if (len + m.size > max_payload_length)                             // :210-211, :261-262
-                return m.err = WS_FRAME_PARSE_ERROR_PAYLOAD_TOO_BIG;
-            if (!m.buf) msg_reserve_exact(m, b, k);
-            if (!msg_append(m, b.wire + off, (size_t)len))
-                return m.err = api_fail(NETC_GPU_ENOMEM, "ingest: message buffer");
-            if (b0 & 0x80) {                                                    // FIN: the message (:340-346)
-                if (m.opcode == WS_OPCODE_TEXT && !msg_append(m, (const uint8_t*)"", 1))
-                    return m.err = api_fail(NETC_GPU_ENOMEM, "ingest: message buffer");
-                if (!m.buf && !(m.buf = (uint8_t*)malloc(1)))   // an empty message still gets a buffer
-                    return m.err = api_fail(NETC_GPU_ENOMEM, "ingest: message buffer");
-                message->opcode = m.opcode;
-                message->buffer = m.buf;
-                message->payload_length = m.size;
+            if (!m.m.buf && len + m.m.size <= max_payload_length) msg_reserve_exact(m.m, b, k);
+            const int r = msg_add_frame(m.m, b.b0[k], b.wire + off, len, max_payload_length, message);
+            if (r == NETC_GPU_ENOMEM) return m.err = api_fail(NETC_GPU_ENOMEM, "ingest: message buffer");
+            if (r < 0) return m.err = r;
+            if (r == 0) {
                 m.end_pos = b.stream_offset + b.hdr[k + 1];
-                m.buf = nullptr;
-                m.size = m.cap = 0;
                 return 0;
             }
         }
@@ -678,37 +605,9 @@ int netc_ws_ingest_next_message(struct netc_ws_ingest* g, struct ws_message* mes
     }
 }
 
-// Remove the socket's bytes up to stream position `to` (<= in_pos: the ring holds a copy of
-// them, read with MSG_PEEK).  TCP discards them without a copy (recv with MSG_TRUNC and no
-// buffer); other stream sockets refuse that (EFAULT, nothing taken) and read into scratch.
-static int sock_consume(netc_ws_ingest* g, int fd, uint64_t to) {
-    RouteState& rs = g->route;
-    while (rs.sock_pos < to) {
-        const uint64_t want = to - rs.sock_pos;
-        ssize_t r;
-        if (rs.tcp) {
-            r = recv(fd, nullptr, (size_t)want, MSG_TRUNC | MSG_DONTWAIT);
-            if (r < 0 && errno == EFAULT) {
-                rs.tcp = 0;   // this socket copies: use the scratch from now on
-                continue;
-            }
-        } else {
-            if (!rs.scratch && !(rs.scratch = (uint8_t*)malloc(kScratch)))
-                return api_fail(NETC_GPU_ENOMEM, "ingest: discard buffer");
-            r = recv(fd, rs.scratch, (size_t)(want < kScratch ? want : kScratch), MSG_DONTWAIT);
-        }
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) {   // the bytes were peeked, so they are there: the socket has failed
-            const int saved = r < 0 ? errno : ECONNRESET;
-            api_fail(NETC_WS_INGEST_ERECV, "ingest: removing delivered bytes from socket %d: %s", fd,
-                     strerror(saved));
-            netc_errno_reason = kBadRecv;
-            errno = saved;
-            return NETC_WS_INGEST_ERECV;
-        }
-        rs.sock_pos += (uint64_t)r;
-    }
-    return 0;
+// remove the route's socket's bytes up to stream position `to` (<= in_pos: the ring holds a copy)
+static int route_consume(netc_ws_ingest* g, uint64_t to) {
+    return sock_consume(g->route, to, "ingest", "delivered");
 }
 
 // ws_parse_frame on a socket attached to a ring (include/ws/route.h): the reference's receive
@@ -737,18 +636,17 @@ static int sock_consume(netc_ws_ingest* g, int fd, uint64_t to) {
 // peek what the socket has past the ring's bytes into the ring, then take it out of the socket
 // but for the hostage; returns new bytes (> 0), 0 when nothing new, or a code (CLOSED, ...)
 static long route_take(netc_ws_ingest* g, int fd) {
-    RouteState& rs = g->route;
-    const int held = (int)(g->in_pos - rs.sock_pos);   // 0 or 1
+    const int held = (int)(g->in_pos - g->route.sock_pos);   // 0 or 1
     long n = ring_recv(g, fd, held);
     if (n > 0) {
-        if (int e = sock_consume(g, fd, g->in_pos - 1)) return e;
+        if (int e = route_consume(g, g->in_pos - 1)) return e;
         return n;
     }
     if (n == 0 && held) {   // only the hostage: release it and look once more
-        if (int e = sock_consume(g, fd, g->in_pos)) return e;
+        if (int e = route_consume(g, g->in_pos)) return e;
         n = ring_recv(g, fd, 0);
         if (n > 0) {
-            if (int e = sock_consume(g, fd, g->in_pos - 1)) return e;
+            if (int e = route_consume(g, g->in_pos - 1)) return e;
         }
     }
     return n;
@@ -773,7 +671,7 @@ static int gpu_route(void* ctx, int sockfd, struct ws_frame_parsing_state* state
         if (r == 0) {
             // everything the ring read is delivered: the hostage goes too (a failing socket is
             // reported by the next call, after this message)
-            if (g->msg.end_pos == g->in_pos && !g->msg.buf) (void)sock_consume(g, sockfd, g->in_pos);
+            if (g->msg.end_pos == g->in_pos && !g->msg.m.buf) (void)route_consume(g, g->in_pos);
             else route_pump(g, sockfd);
             state->message = m;
             return 0;
@@ -793,28 +691,17 @@ static int gpu_route(void* ctx, int sockfd, struct ws_frame_parsing_state* state
     }
 }
 
-// the identity of an open socket (device, inode), to tell a reused descriptor from the attached one
-static bool sock_identity(int fd, uint64_t* dev, uint64_t* ino) {
-    struct stat st;
-    if (fstat(fd, &st) != 0 || !S_ISSOCK(st.st_mode)) return false;
-    *dev = (uint64_t)st.st_dev;
-    *ino = (uint64_t)st.st_ino;
-    return true;
-}
-
 // close() on the attached socket (close tracking, include/ws/route.h): the ring lets go of it
 static void ingest_close_hook(void* ctx, int sockfd) { (void)netc_ws_gpu_detach(sockfd); }
 
 int netc_ws_gpu_attach(int sockfd, struct netc_ws_ingest* ring) {
     if (!ring) return api_fail(NETC_GPU_EINVAL, "attach: null ring");
-    uint64_t dev = 0, ino = 0;
-    if (!sock_identity(sockfd, &dev, &ino)) return api_fail(NETC_GPU_EINVAL, "attach: %d is not an open socket", sockfd);
-    RouteState& rs = ring->route;
+    SockId id;
+    if (!sock_identity(sockfd, &id)) return api_fail(NETC_GPU_EINVAL, "attach: %d is not an open socket", sockfd);
+    PeekSock& rs = ring->route;
     if (rs.fd >= 0) {
-        uint64_t d2 = 0, i2 = 0;
-        const bool same = rs.fd == sockfd && rs.dev == dev && rs.ino == ino;
-        if (same) return 0;   // already serving this connection
-        if (sock_identity(rs.fd, &d2, &i2) && d2 == rs.dev && i2 == rs.ino)
+        if (rs.fd == sockfd && rs.id == id) return 0;   // already serving this connection
+        if (same_socket(rs.fd, rs.id))
             return api_fail(NETC_GPU_EINVAL, "attach: the ring already serves socket %d (one ring, one connection)",
                             rs.fd);
         // its connection was closed without a detach: drop the stale route if it is still ours
@@ -825,19 +712,15 @@ int netc_ws_gpu_attach(int sockfd, struct netc_ws_ingest* ring) {
     // a ring carries one connection's stream: a used one would splice two streams together
     if (ring->in_pos != 0 || ring->closed || ring->sticky || ring->msg.err)
         return api_fail(NETC_GPU_EINVAL, "attach: the ring has already carried a stream (create a fresh one)");
-    int type = 0, domain = 0;
-    socklen_t tl = sizeof type, dl = sizeof domain;
-    if (getsockopt(sockfd, SOL_SOCKET, SO_TYPE, &type, &tl) != 0 || type != SOCK_STREAM)
-        return api_fail(NETC_GPU_EINVAL, "attach: socket %d is not a stream socket", sockfd);
-    (void)getsockopt(sockfd, SOL_SOCKET, SO_DOMAIN, &domain, &dl);
+    const int kind = stream_socket_kind(sockfd);
+    if (kind == kNotStream) return api_fail(NETC_GPU_EINVAL, "attach: socket %d is not a stream socket", sockfd);
     const int r = netc_ws_route_attach(sockfd, gpu_route, ring);
     if (r != 0)
         return api_fail(NETC_GPU_EINVAL, "attach: socket %d: %s", sockfd,
                         errno == EBUSY ? "another route serves it" : "out of range");
     rs.fd = sockfd;
-    rs.dev = dev;
-    rs.ino = ino;
-    rs.tcp = domain == AF_INET || domain == AF_INET6;
+    rs.id = id;
+    rs.tcp = kind == kStreamTcp;
     rs.sock_pos = 0;
     (void)netc_ws_route_on_close(sockfd, ingest_close_hook);
     return 0;
@@ -862,7 +745,7 @@ int netc_ws_ingest_debug_state(const struct netc_ws_ingest* g, uint64_t* out8) {
     out8[2] = g->msg.end_pos;
     out8[3] = (uint64_t)g->count;
     out8[4] = g->cur >= 0 ? g->slots[g->cur].fill : ~0ull;
-    out8[5] = g->msg.size;
+    out8[5] = g->msg.m.size;
     out8[6] = (uint64_t)(int64_t)(g->sticky ? g->sticky : g->msg.err);
     out8[7] = g->prev >= 0 ? g->slots[g->prev].pos + g->slots[g->prev].cut : 0;
     return 0;
@@ -879,9 +762,7 @@ int netc_ws_batch_payload(const struct netc_ws_batch* b, uint64_t k, uint64_t* o
     if (!b || !offset || !length || k >= b->nframes) return NETC_GPU_EINVAL;
     // header bytes are as received (the unmask touches payloads only)
     const uint64_t h = b->hdr[k];
-    const uint8_t second = b->wire[h + 1];
-    const uint64_t code = second & 0x7F;
-    const uint64_t hl = 2 + (code == 126 ? 2 : (code == 127 ? 8 : 0)) + ((second & 0x80) ? 4 : 0);
+    const uint64_t hl = ws_header_len_of(b->wire[h + 1]);
     *offset = h + hl;
     *length = b->hdr[k + 1] - (h + hl);
     return 0;

@@ -16,6 +16,7 @@
 
 #include "ws_decode_gpu.h"
 #include "ws_mask_gpu.h"
+#include "ws_ring_host.h"   // DeviceGuard
 
 extern "C" {
 #include "../../include/ws/mask.h"
@@ -75,24 +76,6 @@ int fail(int code, const char* fmt, ...) {
 int fail_hip(int code, const char* what, hipError_t e) {
     return fail(code, "%s: %s (%d)", what, hipGetErrorString(e), (int)e);
 }
-
-// Selects `device` for the calling thread for the lifetime of the guard.  The hot
-// path (the device is already current) costs one hipGetDevice (a thread-local read
-// in the runtime) and nothing on exit.
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int device) {
-        err = hipGetDevice(&prev);
-        if (err != hipSuccess || prev == device) return;
-        err = hipSetDevice(device);
-        switched = err == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (switched) (void)hipSetDevice(prev);
-    }
-};
 
 // device count, queried once per process (HIP's device list is fixed at runtime init)
 int cached_device_count() {
